@@ -7,8 +7,14 @@ pairs already resident in HBM (BASELINE.json config C3; C4 = the same per GPU ov
 launched by torch.distributed.run, RCCL gradient all-reduce).  Prints ONE JSON line on rank 0.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--config fusion|thermal|rgb]
+                  [--dump-outputs DIR] [--full]
   python bench.py --config gradcam [--batch 32]   # C5: fusion predict + Grad-CAM maps per sample
   python bench.py --config pipeline [--batch 64]  # §8f row 3: GPU train transforms per pair
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.
+--full adds what takes runs of its own: the other precision modes, the in-run logits parity
+against the CPU oracle, the GEMM roofline replays and the CPU baseline (each with its --no-*
+switch); without it those fields of the line are null.
 """
 import argparse
 import json
@@ -52,7 +58,14 @@ def parse():
                     help="replay the train step as one HIP graph (default: eager, measured faster: "
                          "the two encoder streams overlap better than the graph's branches)")
     ap.add_argument("--no-graph", action="store_true", help="eager (the default; kept for scripts)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also time the other precision modes, check the "
+                         "logits against the CPU oracle, replay the step's GEMMs for the roofline "
+                         "and time the CPU baseline (default: the timed steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, at most 64 MB in all; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip it")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="CPU baseline threads (default: the host's physical cores, lscpu "
                          "sockets x cores per socket, BASELINE.md)")
@@ -64,9 +77,10 @@ def parse():
                          "north_star's 1e-3 logits bar with margin, DESIGN.md §4), with no "
                          "set_precision call; the other modes are timed beside it")
     ap.add_argument("--no-alt-precision", action="store_true",
-                    help="skip timing the other precision modes")
+                    help="with --full: skip timing the other precision modes")
     ap.add_argument("--no-parity", action="store_true",
-                    help="skip the in-run logits parity check against the CPU oracle")
+                    help="with --full: skip the in-run logits parity check against the CPU "
+                         "oracle")
     args = ap.parse_args()
     if args.batch is None:
         args.batch = 32 if args.config == "gradcam" else 64
@@ -336,6 +350,28 @@ def gemm_roofline(fwd_bwd, tail, replays=3):
             "x3_launches": sum(1 for r in rec if r[4] == 3.0 * r[1])}
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: the files' total
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor} as DIR/<name>.npy, float64 for 64-bit tensors and float32
+    for the rest.  Each array gets an equal share of DUMP_BYTES; a longer one is cut to a fixed
+    sample of its flattened elements (seeded indices, ascending: the same elements in every
+    run), so two builds run with the same arguments compare output for output."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    # elements per array: 8 bytes each at the most, after 1 KiB set aside for its .npy header
+    cap = (DUMP_BYTES // len(arrays) - 1024) // 8
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.to(torch.float64 if t.dtype in (torch.float64, torch.int64) else torch.float32)
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
+
+
 def main_gradcam(args, rank, world, dev):
     """C5 (grad_cam_visualization.py visualize_multimodal :561-632, batched): per batch of B
     samples resident in HBM, one eval fusion forward under no_grad (softmax, argmax), then
@@ -376,6 +412,8 @@ def main_gradcam(args, rank, world, dev):
         from dfu_hip import graphs
         # the hooks' Python runs once, at capture; replays rewrite the same buffers
         graph = graphs.try_capture(step, log=None if rank == 0 else False)
+        # the buffers the replays write (the eager trial below rebinds outs to fresh tensors)
+        graph_outs = dict(outs)
         if graph is not None:
             graph.replay()
             torch.cuda.synchronize()
@@ -422,13 +460,15 @@ def main_gradcam(args, rank, world, dev):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, gpu_s = t.tolist()
         gpu_ms = gpu_s * 1000.0
-    gr = gemm_roofline(step, lambda: None)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, graph_outs if graph is not None else outs)
+    gr = gemm_roofline(step, lambda: None) if args.full else None
     value = args.batch * args.gpus * args.steps / elapsed
     per_step_s = gpu_ms / 1000.0 / args.steps
     achieved = args.batch * FLOPS_PER_UNIT["gradcam"] / per_step_s / 1e12
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline_gradcam(baseline_threads(args))
             except Exception as e:
@@ -440,7 +480,7 @@ def main_gradcam(args, rank, world, dev):
             "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed * 1000.0 / args.steps, 3), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": arithmetic_label(model),
-            "precision": args.precision,
+            "full": args.full, "precision": args.precision,
             "precision_source": "library default (no set_precision call)"
             if args.precision == Fn.DEFAULT_PRECISION else "--precision",
             "data": "synthetic 224x224 RGB+thermal pairs (uint8 U{0..255}, reference "
@@ -452,7 +492,8 @@ def main_gradcam(args, rank, world, dev):
                        "image": 224, "parallelism": f"replicas{args.gpus}",
                        "hip_graph": graph is not None, "graph_vs_eager_ms": choice or None,
                        "dist": args.dist},
-            "roofline": {"bound": "mfma", "achieved": round(gr["achieved"], 1),
+            "roofline": None if gr is None else {
+                         "bound": "mfma", "achieved": round(gr["achieved"], 1),
                          "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(gr["achieved"] / PEAK_BF16_TFLOPS, 4),
                          "traffic": None, "traffic_note": "PMC traffic measured on the C3 bench "
@@ -498,9 +539,11 @@ def main_pipeline(args, rank, world, dev):
     staged = [(rgb_pre.stage(r, pr), th_pre.stage(t, pt)) for r, pr, t, pt in hosts]
     torch.cuda.synchronize()
 
+    outs = {}
+
     def step(i):
         a, b = staged[i % NB]
-        return rgb_pre.run(a), th_pre.run(b)
+        outs["rgb"], outs["thermal"] = rgb_pre.run(a), th_pre.run(b)
     for i in range(max(1, args.warmup)):
         step(i)
     if world > 1:
@@ -521,14 +564,18 @@ def main_pipeline(args, rank, world, dev):
         t = torch.tensor([elapsed, gpu_s], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, gpu_s = t.tolist()
-    # PCIe-inclusive: host packing + H2D + kernels, same batches
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        r, pr, t, pt = hosts[i % NB]
-        rgb_pre(r, pr), th_pre(t, pt)
-    torch.cuda.synchronize()
-    incl = args.batch * args.steps / (time.perf_counter() - t1)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs)
+    incl = None
+    if args.full:
+        # PCIe-inclusive: host packing + H2D + kernels, same batches
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            r, pr, t, pt = hosts[i % NB]
+            rgb_pre(r, pr), th_pre(t, pt)
+        torch.cuda.synchronize()
+        incl = args.batch * args.steps / (time.perf_counter() - t1)
     # algorithmic HBM bytes per pair (both modalities): source read, horizontal-pass rows
     # written + read, resized image written + read (+ once more by the contrast statistics when
     # drawn: not counted), fp32 NCHW output written
@@ -539,7 +586,7 @@ def main_pipeline(args, rank, world, dev):
     value = args.batch * args.gpus * args.steps / elapsed
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import transforms_ref as TR
             r, pr, t, pt = hosts[0]
@@ -560,7 +607,7 @@ def main_pipeline(args, rank, world, dev):
             "value": round(value, 2), "unit": "pairs/sec", "n_gpus": args.gpus,
             "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed * 1000.0 / args.steps, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+            "scaling": "weak", "vs_baseline": None, "dtype": "u8", "full": args.full,
             "data": "synthetic decoded 640x480 RGB + thermal frames (uint8 uniform), "
                     "parameters drawn in torchvision's order (seeded)",
             "config": {"workload": "§8f row 3 input pipeline: Resize(224) + flips + "
@@ -568,7 +615,7 @@ def main_pipeline(args, rank, world, dev):
                                    "(p 0.6) + ToTensor + Normalize, both modalities",
                        "per_gpu_batch": args.batch, "source": f"{W0}x{H0}",
                        "parallelism": f"replicas{args.gpus}", "dist": args.dist},
-            "pcie_inclusive_pairs_per_sec": round(incl, 1),
+            "pcie_inclusive_pairs_per_sec": None if incl is None else round(incl, 1),
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS,
                          "unit": "GB/s", "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": None,
                          "kernel": "augment pipeline (8 launches per step: 2 resize passes, "
@@ -749,12 +796,15 @@ def main():
     reducer = parallel.GradAllReducer(opt.flat, overlap=not use_graph) if world > 1 else None
     rgb, th, y = synthetic(args.batch, dev, seed=42 + rank)
 
+    last = {}  # what the latest step handed its caller (--dump-outputs)
+
     def fwd_bwd():
         opt.zero_grad()
         if reducer is not None and reducer.overlap:
             reducer.start()
         out = fwd(model, rgb, th)
         loss = crit(out, y)
+        last["logits"], last["loss"] = out, loss
         loss.backward()
         Fn.join_grad_streams()  # the thermal branch's side stream rejoins (graph capture needs it)
         return loss
@@ -802,9 +852,13 @@ def main():
             tail()
 
     elapsed, gpu_ms, durs = timed_steps(step, args.steps, world, dev)
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's logits and loss, and the parameters and gradients it left
+        dump_outputs(args.dump_outputs, {"logits": last["logits"], "loss": last["loss"],
+                                         "params": opt.flat.data, "grads": opt.flat.grad})
     # the other precision modes, same model and batch, eager (reported beside `value`)
     alts = []
-    if not args.no_alt_precision and graph is None:
+    if args.full and not args.no_alt_precision and graph is None:
         for other in [m for m in ("bf16", "bf16x3", "parity") if m != args.precision]:
             old = Fn.set_precision(other)
             try:
@@ -817,16 +871,18 @@ def main():
                          "value": round(args.batch * args.gpus * args.steps / a_el, 2),
                          "ms_per_step": round(a_el * 1000.0 / args.steps, 3),
                          "gpu_ms_per_step_median": round(pct(a_durs, 0.5), 3)})
-    # every rank runs the instrumented steps (their all-reduces must pair up); rank 0 reports
-    opt.check_grads = True
-    gr = gemm_roofline(fwd_bwd, tail)
+    gr = None
+    if args.full:
+        # every rank runs the instrumented steps (their all-reduces must pair up); rank 0 reports
+        opt.check_grads = True
+        gr = gemm_roofline(fwd_bwd, tail)
     imgs = args.batch * args.gpus * args.steps
     value = imgs / elapsed
     per_gpu_step_s = (gpu_ms / 1000.0) / args.steps
     achieved = args.batch * FLOPS_PER_UNIT[args.config] / per_gpu_step_s / 1e12
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline(args.config, baseline_threads(args))
             except Exception as e:  # never lose the GPU line over the baseline
@@ -840,7 +896,7 @@ def main():
         for alt in alts:
             modes[alt["precision"]] = {k: v for k, v in alt.items() if k != "precision"}
         parity = None
-        if world == 1 and not args.no_parity:
+        if args.full and world == 1 and not args.no_parity:
             try:
                 pthreads = (cpu or {}).get("cores") or min(16, baseline_threads(args))
                 parity = parity_check(args.config, dev, args.batch, pthreads)
@@ -862,6 +918,7 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": arithmetic_label(model),
+            "full": args.full,
             "precision": args.precision,
             "precision_source": precision_source,
             "precision_note": PRECISION_NOTE.get(args.precision),
@@ -880,7 +937,8 @@ def main():
             "value_meets_parity_bar": None if parity is None or "error" in parity
             else parity[args.precision]["meets_bar"],
             "parity": parity,
-            "roofline": {"bound": "mfma", "achieved": round(gr["achieved"], 1),
+            "roofline": None if gr is None else {
+                         "bound": "mfma", "achieved": round(gr["achieved"], 1),
                          "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(gr["achieved"] / PEAK_BF16_TFLOPS, 4),
                          "traffic": None if traffic is None else round(traffic),

@@ -19,6 +19,38 @@ def _run(extra_env):
     return p, [json.loads(ln) for ln in lines]
 
 
+def test_dump_outputs_is_bounded_typed_and_repeatable(tmp_path):
+    """--dump-outputs: float32 files (float64 for 64-bit tensors), at most 64 MB in all, a long
+    array cut to the same seeded sample of its elements on every call."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    big = torch.arange(5_000_000, dtype=torch.float32)
+    arrays = {"logits": torch.randn(64, 2).bfloat16(), "loss": torch.tensor(0.5),
+              "pred": torch.arange(5), "params": big, "grads": -big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    total = 0
+    for name, t in arrays.items():
+        a, b = (np.load(tmp_path / d / f"{name}.npy") for d in ("a", "b"))
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == (np.float64 if t.dtype == torch.int64 else np.float32)
+        assert np.array_equal(a, b)
+        if t.numel() < 1_000_000:
+            assert a.shape == tuple(t.shape) and np.array_equal(a, t.float().numpy())
+    assert total <= bench.DUMP_BYTES
+    # the bound holds with every array long and 8 bytes an element, .npy headers included
+    wide = {"a": torch.arange(5_000_000), "b": torch.arange(5_000_000).double()}
+    bench.dump_outputs(str(tmp_path / "w"), wide)
+    sizes = [os.path.getsize(tmp_path / "w" / f"{n}.npy") for n in wide]
+    assert 60 << 20 < sum(sizes) <= bench.DUMP_BYTES
+    assert all(np.load(tmp_path / "w" / f"{n}.npy").dtype == np.float64 for n in wide)
+    p, g = np.load(tmp_path / "a" / "params.npy"), np.load(tmp_path / "a" / "grads.npy")
+    assert 0 < p.size < big.numel() and np.array_equal(p, -g)  # the same elements of both
+    assert np.all(np.diff(p) >= 0) and p.max() > big.numel() // 2  # drawn from the whole array
+
+
 def test_gpus2_without_enough_devices_fails():
     import torch
     if torch.cuda.device_count() >= 2:

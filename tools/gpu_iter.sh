@@ -9,7 +9,7 @@ if [ -n "$2" ]; then
 fi
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.log 2>&1 || { echo "smoke rc=$?"; tail -20 $OUT/smoke_$TAG.log; exit 1; }
 tail -3 $OUT/smoke_$TAG.log
-timeout -k 10 600 python bench.py ${BENCH_ARGS:---no-cpu-baseline} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { echo "bench rc=$?"; tail -20 $OUT/bench_$TAG.err; exit 1; }
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:---no-cpu-baseline} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { echo "bench rc=$?"; tail -20 $OUT/bench_$TAG.err; exit 1; }
 python -c "
 import json; d=json.load(open('$OUT/bench_$TAG.json'))
 print('value', d['value'], 'ms', d['ms_per_step'], 'gpu median', d['gpu_step_ms']['median'], 'modes', {k: v['value'] for k, v in d['precision_modes'].items()}, 'parity', {k: v['max_abs_logits_vs_fp32_oracle'] for k, v in (d['parity'] or {}).items() if isinstance(v, dict)}, 'gemm', d['roofline']['achieved'], d['roofline']['avg_launch_us'])"
