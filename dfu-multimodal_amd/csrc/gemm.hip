@@ -12,30 +12,25 @@ using namespace dfu;
 
 namespace {
 
+inline int round8(int x) { return (x + 7) & ~7; }
+inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
 constexpr int kCUs = 256;
-constexpr int kTM[NTILES] = {128, 256, 128, 256, 128, 128, 256, 256, 192, 256, 128};
-constexpr int kTN[NTILES] = {128, 128, 256, 256, 128, 128, 256, 256, 256, 64, 64};
-constexpr int kOcc[NTILES] = {1, 1, 1, 1, 2, 2, 1, 1, 1, 1, 2};  // workgroups per CU
-// the tile whose fitted step time a variant borrows (the persistent phased 256x256: the phased)
-constexpr int kBase[NTILES] = {0, 1, 2, 3, 4, 5, 6, 6, 6, 9, 10};
-constexpr bool kTailOK[NTILES] = {true, false, false, false, true, false, false, false, false,
-                                  false, false};
-// Wave-quantisation cost model: a launch takes ceil(tiles * splits / 256) rounds (one 512-thread
-// workgroup per CU), each costing kRoundUs (prologue fill + epilogue) + k-steps * kStepUs.
-// Fitted on MI355X to tools/gemm_bench.py --sweep (ViT qkv K=768 vs fc2 K=3072 forward rows,
-// r01): 128x128 0.57 us/step + 4.8 us/round ... 256x256 1.41 us/step + 13.9 us/round, i.e.
-// 256x256 moves 1.62x more MFMA work per microsecond than 128x128.
-// The 2-per-CU 128x128 variant: two co-resident workgroups share the MFMA pipe (step cost per
-// workgroup ~doubles) but hide each other's fill and epilogue.
-// (the phased 256x256 kernels are priced high: only the offline-tuned table selects them)
-// (the 64-column tiles are priced high too: only tuned plans select them)
-constexpr double kStepUs[NTILES] = {0.57, 0.89, 0.90, 1.41, 0.70, 0.65, 3.0, 3.0, 3.0, 3.0, 3.0};
-constexpr double kRoundUs[NTILES] = {4.8, 8.3, 7.4, 13.9, 6.1, 6.1, 20.0, 20.0, 20.0, 20.0, 20.0};
+struct TileInfo {  // a row of gemm_table.h: DFU_TILES
+  int tm, tn, occ;  // occ: workgroups per CU
+  bool phased, tail_ok;
+  double step_us, round_us;
+  const Entry* kernels;
+  const int* nkernels;  // (a link-time constant of the tile's own file)
+  int slots() const { return kCUs * occ; }
+  int tiles(int M, int N) const { return cdiv(M, tm) * cdiv(N, tn); }
+};
+#define X(name, tm, tn, occ, phased, tail_ok, step_us, round_us) \
+  {tm, tn, occ, phased, tail_ok, step_us, round_us, kTable##name, &kTable##name##N},
+const TileInfo kTiles[NTILES] = {DFU_TILES(X)};
+#undef X
 constexpr double kSlabGBs = 5000.0;  // split-K: slab write + reduce (read slabs, RMW C)
 constexpr double kReduceLaunchUs = 2.0;
-// Persistent schedule (gemm_kernel.h): a workgroup owning several work units pays one
-// prologue fill for all of them plus, per unit, the epilogue time its MFMAs do not hide.
-constexpr double kUnitUs[NTILES] = {1.0, 1.8, 1.7, 3.0, 1.2, 1.2, 3.0, 3.0, 3.0, 3.0, 3.0};
 // Persistent launches (at most one wave of workgroups, each walking its work units) for the
 // generic tiles (g_persistent) and the persistent phased 256-wide tiles (g_persistent_ps);
 // otherwise one workgroup per unit, which the hardware dispatcher hands to CUs as they free up.
@@ -54,23 +49,13 @@ const int g_wide_reduce = getenv("DFU_GEMM_WIDE_REDUCE") ? atoi(getenv("DFU_GEMM
 int g_tail_split = getenv("DFU_GEMM_TAIL_SPLIT") ? atoi(getenv("DFU_GEMM_TAIL_SPLIT")) : 1;
 
 const Entry* find_entry(int a, int b, int e, int tile) {
-  const Entry* tabs[NTILES] = {kTable128x128, kTable256x128, kTable128x256, kTable256x256,
-                               kTable128x128o2, kTable128x128w4, kTable256x256p8,
-                               kTable256x256ps, kTable192x256ps, kTable256x64,
-                               kTable128x64o2};
-  const int ns[NTILES] = {kTable128x128N, kTable256x128N, kTable128x256N, kTable256x256N,
-                          kTable128x128o2N, kTable128x128w4N, kTable256x256p8N,
-                          kTable256x256psN, kTable192x256psN, kTable256x64N,
-                          kTable128x64o2N};
-  for (int i = 0; i < ns[tile]; ++i) {
-    const Entry& en = tabs[tile][i];
+  const TileInfo& ti = kTiles[tile];
+  for (int i = 0; i < *ti.nkernels; ++i) {
+    const Entry& en = ti.kernels[i];
     if (en.a == a && en.b == b && en.e == e) return &en;
   }
   return nullptr;
 }
-
-inline int round8(int x) { return (x + 7) & ~7; }
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 struct Plan {
   const Entry* entry = nullptr;
@@ -113,10 +98,8 @@ const TunedPlan* find_tuned_key(const dfu_gemm_desc* d, int epi) {
 
 const TunedPlan* find_tuned(const dfu_gemm_desc* d) {
   const int epi = d->epilogue | (d->x3_pairs ? kX3Key : 0);
-#ifndef DFU_NO_F16_TUNED  // (A/B builds only: the fp16 GEMMs on the bf16 shapes' plans)
   if (d->operand_type == 1)
     if (const TunedPlan* t = find_tuned_key(d, epi | kF16Key)) return t;
-#endif
   return find_tuned_key(d, epi);
 }
 
@@ -138,7 +121,8 @@ Plan plan_gemm(const dfu_gemm_desc* d) {
     if (d->tile > 0 && d->tile - 1 != t) continue;
     const Entry* en = find_entry(d->a_mode, d->b_mode, epi_key(d), t);
     if (!en) continue;
-    const int tiles = cdiv(d->M, kTM[t]) * cdiv(d->N, kTN[t]);
+    const TileInfo& ti = kTiles[t];
+    const int tiles = ti.tiles(d->M, d->N);
     int s_lo = 1, s_hi = 1;
     if (acc_epi) {
       if (d->split_k > 0) s_lo = s_hi = d->split_k;
@@ -148,11 +132,10 @@ Plan plan_gemm(const dfu_gemm_desc* d) {
       const int kps = cdiv(ktiles, s);
       const int se = cdiv(ktiles, kps);
       if (se != s && s != s_lo) continue;
-      const int slots = kCUs * kOcc[t];
-      const int rounds = cdiv(tiles * se, slots);
-      double cost = (g_persistent && tiles * se > slots)
-                        ? kRoundUs[t] + rounds * (kps * kStepUs[t] + kUnitUs[t])
-                        : rounds * (kRoundUs[t] + kps * kStepUs[t]);
+      // one workgroup per unit, whatever schedule launch() then runs: the plan (and with it
+      // the summation order) does not depend on dfu_gemm_set_persistent
+      const int rounds = cdiv(tiles * se, ti.slots());
+      double cost = rounds * (ti.round_us + kps * ti.step_us);
       if (se > 1)
         cost += kReduceLaunchUs + 4.0 * (se + 2) * (double)d->M * d->N / (kSlabGBs * 1e3);
       if (cost < best.cost) {
@@ -249,9 +232,11 @@ struct Tail {
 // and the last of each tile reads them all back, ~2 x R x S x TM x TN x 4 bytes at ~5 TB/s, plus
 // ~3 us (fitted on MI355X with tools/gemm_step_profile.py --tail-ab: K >= ~2304 launches gain
 // 7-40 us, K <= 1024 ones would lose up to 11).  Used only if the net gain is positive.
-Tail tail_plan(int tiles, int slots, int ktiles, int tm, int tn, double step_us) {
-  Tail best;
-  if (!g_tail_split) return best;
+Tail tail_plan(const dfu_gemm_desc* d, const Plan& pl) {
+  const TileInfo& ti = kTiles[pl.tile];
+  Tail best;  // (F32_ACC aside, every epilogue plans split 1: an unsplit launch)
+  if (!g_tail_split || !pl.entry || d->epilogue == DFU_EPI_F32_ACC || !ti.tail_ok) return best;
+  const int tiles = ti.tiles(d->M, d->N), slots = ti.slots(), ktiles = cdiv(d->K, BK);
   const int R = tiles % slots;
   if (R == 0) return best;
   int smax = slots / R;
@@ -262,8 +247,8 @@ Tail tail_plan(int tiles, int slots, int ktiles, int tm, int tn, double step_us)
     const int kps = cdiv(ktiles, S);
     const int se = cdiv(ktiles, kps);
     if (se != S) continue;
-    const double bytes = (double)R * S * tm * tn * 4;
-    const double gain = (ktiles - kps) * step_us - (3.0 + 2.0 * bytes / 5e6);
+    const double bytes = (double)R * S * ti.tm * ti.tn * 4;
+    const double gain = (ktiles - kps) * ti.step_us - (3.0 + 2.0 * bytes / 5e6);
     if (gain > best_gain) {
       best_gain = gain;
       best.s = S;
@@ -273,15 +258,119 @@ Tail tail_plan(int tiles, int slots, int ktiles, int tm, int tn, double step_us)
   if (best.s < 2) return Tail();
   best.full = tiles - R;
   best.r = R;
-  best.bytes = (int64_t)best.s * R * tm * tn * 4;
+  best.bytes = (int64_t)best.s * R * ti.tm * ti.tn * 4;
   return best;
 }
 
-Tail tail_for(const dfu_gemm_desc* d, const Plan& pl) {
-  if (!pl.entry || d->epilogue == DFU_EPI_F32_ACC || !kTailOK[pl.tile]) return Tail();
-  const int tiles = cdiv(d->M, kTM[pl.tile]) * cdiv(d->N, kTN[pl.tile]);
-  return tail_plan(tiles, kCUs * kOcc[pl.tile], cdiv(d->K, BK), kTM[pl.tile], kTN[pl.tile],
-                   kStepUs[kBase[pl.tile]]);
+// Checks a descriptor and plans it; for dfu_gemm_plan (!launching) only what it always checked.
+int check_desc(const dfu_gemm_desc* d, bool launching, Plan* plan) {
+  const bool acc_epi = d->epilogue == DFU_EPI_F32_ACC;
+  if (launching) {
+    DFU_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "dfu_gemm: bad shape M=%d N=%d K=%d", d->M,
+                  d->N, d->K);
+    const bool a_kc = d->a_mode == DFU_OPND_KMAJOR || d->a_mode == DFU_OPND_CONV_FWD ||
+                      d->a_mode == DFU_OPND_CONV_DGRAD;
+    const bool b_kc = d->b_mode == DFU_OPND_KMAJOR;
+    DFU_CHECK_ARG(!(a_kc || b_kc) || d->K % 8 == 0,
+                  "dfu_gemm: K=%d must be a multiple of 8 for K-contiguous operands", d->K);
+    DFU_CHECK_ARG(d->tile >= 0 && d->tile <= NTILES, "dfu_gemm: bad tile hint %d", d->tile);
+    DFU_CHECK_ARG(d->split_k >= 0, "dfu_gemm: split_k must be >= 0 (0 = auto)");
+    DFU_CHECK_ARG(d->split_k <= 1 || acc_epi, "dfu_gemm: split_k > 1 needs the F32_ACC epilogue");
+  }
+  DFU_CHECK_ARG(d->operand_type == 0 || d->operand_type == 1, "dfu_gemm: bad operand_type %d",
+                d->operand_type);
+  if (d->epilogue == DFU_EPI_F16_DUAL || d->epilogue == DFU_EPI_F16_GELU) {
+    DFU_CHECK_ARG(d->operand_type == 1, "dfu_gemm: the F16 epilogues need operand_type 1");
+    DFU_CHECK_ARG((d->epilogue == DFU_EPI_F16_DUAL && d->aux_out == nullptr) ||
+                      (d->aux_out != nullptr && d->ldaux_out >= d->N),
+                  "dfu_gemm: F16_GELU needs aux_out (F16_DUAL: NULL or ldaux_out >= N)");
+    DFU_CHECK_ARG(d->epilogue != DFU_EPI_F16_GELU || d->ldc >= 2LL * d->N,
+                  "dfu_gemm: F16_GELU needs ldc >= 2N");
+  }
+  const Plan pl = *plan = plan_gemm(d);
+  if (!pl.entry) {
+    if (launching)
+      dfu_set_error("dfu_gemm: unsupported combination a_mode=%d b_mode=%d epilogue=%d tile=%d "
+                    "operand_type=%d", d->a_mode, d->b_mode, d->epilogue, d->tile,
+                    d->operand_type);
+    else
+      dfu_set_error("dfu_gemm_plan: unsupported combination");
+    return DFU_E_UNSUPPORTED;
+  }
+  if (!launching) return DFU_OK;
+  if (d->epilogue == DFU_EPI_BF16_DGELU && d->stats != nullptr && pl.tile != T256x256ps) {
+    // the dGELU column sums exist in the persistent phased 256x256 epilogue only; the caller
+    // then sums the columns itself
+    dfu_set_error("dfu_gemm: dGELU column sums need the persistent 256x256 tile (plan: %d)",
+                  pl.tile + 1);
+    return DFU_E_UNSUPPORTED;
+  }
+  if (d->epilogue == DFU_EPI_X3_GELU) {
+    DFU_CHECK_ARG(pl.tile == T256x256ps, "dfu_gemm: X3_GELU needs the persistent 256x256 tile");
+    DFU_CHECK_ARG(d->aux_out != nullptr && d->ldaux_out >= d->N && d->ldc >= 3LL * d->N,
+                  "dfu_gemm: X3_GELU needs aux_out (ldaux_out >= N) and ldc >= 3N");
+  }
+  DFU_CHECK_ARG(((uintptr_t)d->A & 15) == 0 && ((uintptr_t)d->B & 15) == 0,
+                "dfu_gemm: A and B must be 16-byte aligned");
+  if (d->a_mode == DFU_OPND_KMAJOR || d->a_mode == DFU_OPND_MNMAJOR)
+    DFU_CHECK_ARG(d->lda % 8 == 0, "dfu_gemm: lda=%lld must be a multiple of 8", (long long)d->lda);
+  if (d->b_mode == DFU_OPND_KMAJOR || d->b_mode == DFU_OPND_MNMAJOR)
+    DFU_CHECK_ARG(d->ldb % 8 == 0, "dfu_gemm: ldb=%lld must be a multiple of 8", (long long)d->ldb);
+  if (d->a_mode == DFU_OPND_MNMAJOR)
+    DFU_CHECK_ARG(d->lda >= round8(d->M), "dfu_gemm: MN-major A needs lda >= round8(M)");
+  if (d->b_mode == DFU_OPND_MNMAJOR)
+    DFU_CHECK_ARG(d->ldb >= round8(d->N), "dfu_gemm: MN-major B needs ldb >= round8(N)");
+  if (d->epilogue == DFU_EPI_BF16_STATS || d->epilogue == DFU_EPI_F32_STATS)
+    DFU_CHECK_ARG(d->stats != nullptr, "dfu_gemm: STATS epilogue needs a stats slab");
+  DFU_CHECK_ARG(d->x3_pairs == 0 || (d->x3_pairs == 1 && d->a_seg > 0 && d->operand_type == 0),
+                "dfu_gemm: x3_pairs (0/1) needs split-pair A (a_seg > 0) and bf16 operands");
+  if (d->a_seg) {
+    const bool conv_a = d->a_mode == DFU_OPND_CONV_FWD;
+    const int nseg = d->x3_pairs ? 2 : 3;  // interleaved pairs: K = 2 a_seg (a_seg % 32 == 0)
+    const int align = d->x3_pairs ? 32 : (conv_a ? 64 : 8);
+    DFU_CHECK_ARG(d->a_lo != nullptr && d->a_seg > 0 && d->a_seg % align == 0 &&
+                      (d->a_mode == DFU_OPND_KMAJOR || conv_a) &&
+                      (conv_a ? d->conv_c == nseg * d->a_seg : (d->K == nseg * d->a_seg &&
+                                                                d->lda == d->a_seg)) &&
+                      ((uintptr_t)d->a_lo & 15) == 0 &&
+                      ((const char*)d->a_lo - (const char*)d->A) % 2 == 0,
+                  "dfu_gemm: split-pair A needs a_lo, a_seg %% 8 == 0 (conv forward: %% 64; "
+                  "x3_pairs: %% 32), K-contiguous or conv-forward A with K (conv_c) = 3 a_seg "
+                  "(x3_pairs: 2 a_seg) and lda = a_seg");
+    DFU_CHECK_ARG(!kTiles[pl.tile].phased,
+                  "dfu_gemm: split-pair A is not supported on the phased tiles (plan %d)",
+                  pl.tile + 1);
+  }
+  if (d->epilogue == DFU_EPI_BF16_DSTATS) {  // retired in round 4 (measured slower); reserved
+    dfu_set_error("dfu_gemm: the DSTATS epilogue is retired");
+    return DFU_E_UNSUPPORTED;
+  }
+
+  const bool conv = d->a_mode >= DFU_OPND_CONV_FWD || d->b_mode >= DFU_OPND_CONV_FWD;
+  if (conv) {
+    DFU_CHECK_ARG(d->conv_n > 0 && d->conv_h > 0 && d->conv_w > 0 && d->conv_c > 0 &&
+                      d->conv_k > 0 && d->conv_r > 0 && d->conv_s > 0 && d->conv_stride > 0 &&
+                      d->conv_p > 0 && d->conv_q > 0,
+                  "dfu_gemm: conv geometry missing");
+    if (d->a_mode == DFU_OPND_CONV_FWD) {
+      DFU_CHECK_ARG(d->conv_c % BK == 0, "dfu_gemm: implicit conv fwd needs C %% 64 == 0");
+      DFU_CHECK_ARG(d->K == d->conv_r * d->conv_s * d->conv_c, "dfu_gemm: conv fwd K != RSC");
+      DFU_CHECK_ARG(d->M == d->conv_n * d->conv_p * d->conv_q, "dfu_gemm: conv fwd M != NPQ");
+    }
+    if (d->a_mode == DFU_OPND_CONV_DGRAD) {
+      DFU_CHECK_ARG(d->conv_k % BK == 0, "dfu_gemm: conv dgrad needs Kout %% 64 == 0");
+      DFU_CHECK_ARG(d->K == d->conv_r * d->conv_s * d->conv_k, "dfu_gemm: conv dgrad K != RSK");
+      DFU_CHECK_ARG(d->M == d->conv_n * d->conv_h * d->conv_w, "dfu_gemm: conv dgrad M != NHW");
+      DFU_CHECK_ARG(d->conv_c % 8 == 0, "dfu_gemm: conv dgrad needs C %% 8 == 0");
+      DFU_CHECK_ARG(d->b_mode == DFU_OPND_CONV_DGRAD_W, "dfu_gemm: conv dgrad needs DGRAD_W B");
+    }
+    if (d->b_mode == DFU_OPND_CONV_WGRAD_X) {
+      DFU_CHECK_ARG(d->conv_c % 8 == 0, "dfu_gemm: conv wgrad needs C %% 8 == 0");
+      DFU_CHECK_ARG(d->N == d->conv_r * d->conv_s * d->conv_c, "dfu_gemm: conv wgrad N != RSC");
+      DFU_CHECK_ARG(d->K == d->conv_n * d->conv_p * d->conv_q, "dfu_gemm: conv wgrad K != NPQ");
+    }
+  }
+  return DFU_OK;
 }
 
 }  // namespace
@@ -298,34 +387,22 @@ extern "C" int64_t dfu_gemm_workspace_bytes(const dfu_gemm_desc* d) {
     if (!g_tail_split) return 0;
     if (d->a_mode == DFU_OPND_CONV_DGRAD && d->conv_stride > 1) {
       int64_t b = 0;
-      for (int t = 0; t < NTILES; ++t) {
-        const int64_t bt = kTailOK[t] ? (int64_t)kCUs * kOcc[t] * kTM[t] * kTN[t] * 4 : 0;
+      for (const TileInfo& ti : kTiles) {
+        const int64_t bt = ti.tail_ok ? (int64_t)ti.slots() * ti.tm * ti.tn * 4 : 0;
         if (bt > b) b = bt;
       }
       return b;
     }
-    return tail_for(d, pl).bytes;
+    return tail_plan(d, pl).bytes;
   }
   return pl.split > 1 ? (int64_t)pl.split * d->M * d->N * 4 : 0;
 }
 
 extern "C" int dfu_gemm_plan(const dfu_gemm_desc* d, int32_t* tile, int32_t* split_k) {
   DFU_CHECK_ARG(d != nullptr && tile != nullptr && split_k != nullptr, "dfu_gemm_plan: null");
-  DFU_CHECK_ARG(d->operand_type == 0 || d->operand_type == 1, "dfu_gemm: bad operand_type %d",
-                d->operand_type);
-  if (d->epilogue == DFU_EPI_F16_DUAL || d->epilogue == DFU_EPI_F16_GELU) {
-    DFU_CHECK_ARG(d->operand_type == 1, "dfu_gemm: the F16 epilogues need operand_type 1");
-    DFU_CHECK_ARG((d->epilogue == DFU_EPI_F16_DUAL && d->aux_out == nullptr) ||
-                      (d->aux_out != nullptr && d->ldaux_out >= d->N),
-                  "dfu_gemm: F16_GELU needs aux_out (F16_DUAL: NULL or ldaux_out >= N)");
-    DFU_CHECK_ARG(d->epilogue != DFU_EPI_F16_GELU || d->ldc >= 2LL * d->N,
-                  "dfu_gemm: F16_GELU needs ldc >= 2N");
-  }
-  const Plan pl = plan_gemm(d);
-  if (!pl.entry) {
-    dfu_set_error("dfu_gemm_plan: unsupported combination");
-    return DFU_E_UNSUPPORTED;
-  }
+  Plan pl;
+  const int rc = check_desc(d, false, &pl);
+  if (rc != DFU_OK) return rc;
   *tile = pl.tile + 1;
   *split_k = pl.split;
   return DFU_OK;
@@ -399,106 +476,9 @@ int launch(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, hipStream_t 
 
 extern "C" int dfu_gemm(const dfu_gemm_desc* d, void* stream) {
   DFU_CHECK_ARG(d != nullptr, "dfu_gemm: null descriptor");
-  DFU_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "dfu_gemm: bad shape M=%d N=%d K=%d", d->M,
-                d->N, d->K);
-  const bool a_kc = d->a_mode == DFU_OPND_KMAJOR || d->a_mode == DFU_OPND_CONV_FWD ||
-                    d->a_mode == DFU_OPND_CONV_DGRAD;
-  const bool b_kc = d->b_mode == DFU_OPND_KMAJOR;
-  DFU_CHECK_ARG(!(a_kc || b_kc) || d->K % 8 == 0,
-                "dfu_gemm: K=%d must be a multiple of 8 for K-contiguous operands", d->K);
-  DFU_CHECK_ARG(d->tile >= 0 && d->tile <= NTILES, "dfu_gemm: bad tile hint %d", d->tile);
-  const bool acc_epi = d->epilogue == DFU_EPI_F32_ACC;
-  DFU_CHECK_ARG(d->split_k >= 0, "dfu_gemm: split_k must be >= 0 (0 = auto)");
-  DFU_CHECK_ARG(d->split_k <= 1 || acc_epi, "dfu_gemm: split_k > 1 needs the F32_ACC epilogue");
-  DFU_CHECK_ARG(d->operand_type == 0 || d->operand_type == 1, "dfu_gemm: bad operand_type %d",
-                d->operand_type);
-  if (d->epilogue == DFU_EPI_F16_DUAL || d->epilogue == DFU_EPI_F16_GELU) {
-    DFU_CHECK_ARG(d->operand_type == 1, "dfu_gemm: the F16 epilogues need operand_type 1");
-    DFU_CHECK_ARG((d->epilogue == DFU_EPI_F16_DUAL && d->aux_out == nullptr) ||
-                      (d->aux_out != nullptr && d->ldaux_out >= d->N),
-                  "dfu_gemm: F16_GELU needs aux_out (F16_DUAL: NULL or ldaux_out >= N)");
-    DFU_CHECK_ARG(d->epilogue != DFU_EPI_F16_GELU || d->ldc >= 2LL * d->N,
-                  "dfu_gemm: F16_GELU needs ldc >= 2N");
-  }
-  const Plan pl = plan_gemm(d);
-  if (!pl.entry) {
-    dfu_set_error("dfu_gemm: unsupported combination a_mode=%d b_mode=%d epilogue=%d tile=%d "
-                  "operand_type=%d", d->a_mode, d->b_mode, d->epilogue, d->tile,
-                  d->operand_type);
-    return DFU_E_UNSUPPORTED;
-  }
-  if (d->epilogue == DFU_EPI_BF16_DGELU && d->stats != nullptr && pl.tile != T256x256ps) {
-    // the dGELU column sums exist in the persistent phased 256x256 epilogue only; the caller
-    // then sums the columns itself
-    dfu_set_error("dfu_gemm: dGELU column sums need the persistent 256x256 tile (plan: %d)",
-                  pl.tile + 1);
-    return DFU_E_UNSUPPORTED;
-  }
-  if (d->epilogue == DFU_EPI_X3_GELU) {
-    DFU_CHECK_ARG(pl.tile == T256x256ps, "dfu_gemm: X3_GELU needs the persistent 256x256 tile");
-    DFU_CHECK_ARG(d->aux_out != nullptr && d->ldaux_out >= d->N && d->ldc >= 3LL * d->N,
-                  "dfu_gemm: X3_GELU needs aux_out (ldaux_out >= N) and ldc >= 3N");
-  }
-  DFU_CHECK_ARG(((uintptr_t)d->A & 15) == 0 && ((uintptr_t)d->B & 15) == 0,
-                "dfu_gemm: A and B must be 16-byte aligned");
-  if (d->a_mode == DFU_OPND_KMAJOR || d->a_mode == DFU_OPND_MNMAJOR)
-    DFU_CHECK_ARG(d->lda % 8 == 0, "dfu_gemm: lda=%lld must be a multiple of 8", (long long)d->lda);
-  if (d->b_mode == DFU_OPND_KMAJOR || d->b_mode == DFU_OPND_MNMAJOR)
-    DFU_CHECK_ARG(d->ldb % 8 == 0, "dfu_gemm: ldb=%lld must be a multiple of 8", (long long)d->ldb);
-  if (d->a_mode == DFU_OPND_MNMAJOR)
-    DFU_CHECK_ARG(d->lda >= round8(d->M), "dfu_gemm: MN-major A needs lda >= round8(M)");
-  if (d->b_mode == DFU_OPND_MNMAJOR)
-    DFU_CHECK_ARG(d->ldb >= round8(d->N), "dfu_gemm: MN-major B needs ldb >= round8(N)");
-  if (d->epilogue == DFU_EPI_BF16_STATS || d->epilogue == DFU_EPI_F32_STATS)
-    DFU_CHECK_ARG(d->stats != nullptr, "dfu_gemm: STATS epilogue needs a stats slab");
-  DFU_CHECK_ARG(d->x3_pairs == 0 || (d->x3_pairs == 1 && d->a_seg > 0 && d->operand_type == 0),
-                "dfu_gemm: x3_pairs (0/1) needs split-pair A (a_seg > 0) and bf16 operands");
-  if (d->a_seg) {
-    const bool conv_a = d->a_mode == DFU_OPND_CONV_FWD;
-    const int nseg = d->x3_pairs ? 2 : 3;  // interleaved pairs: K = 2 a_seg (a_seg % 32 == 0)
-    const int align = d->x3_pairs ? 32 : (conv_a ? 64 : 8);
-    DFU_CHECK_ARG(d->a_lo != nullptr && d->a_seg > 0 && d->a_seg % align == 0 &&
-                      (d->a_mode == DFU_OPND_KMAJOR || conv_a) &&
-                      (conv_a ? d->conv_c == nseg * d->a_seg : (d->K == nseg * d->a_seg &&
-                                                                d->lda == d->a_seg)) &&
-                      ((uintptr_t)d->a_lo & 15) == 0 &&
-                      ((const char*)d->a_lo - (const char*)d->A) % 2 == 0,
-                  "dfu_gemm: split-pair A needs a_lo, a_seg %% 8 == 0 (conv forward: %% 64; "
-                  "x3_pairs: %% 32), K-contiguous or conv-forward A with K (conv_c) = 3 a_seg "
-                  "(x3_pairs: 2 a_seg) and lda = a_seg");
-    DFU_CHECK_ARG(pl.tile != T256x256p8 && pl.tile != T256x256ps && pl.tile != T192x256ps,
-                  "dfu_gemm: split-pair A is not supported on the phased tiles (plan %d)",
-                  pl.tile + 1);
-  }
-  if (d->epilogue == DFU_EPI_BF16_DSTATS) {  // retired in round 4 (measured slower); reserved
-    dfu_set_error("dfu_gemm: the DSTATS epilogue is retired");
-    return DFU_E_UNSUPPORTED;
-  }
-
-  const bool conv = d->a_mode >= DFU_OPND_CONV_FWD || d->b_mode >= DFU_OPND_CONV_FWD;
-  if (conv) {
-    DFU_CHECK_ARG(d->conv_n > 0 && d->conv_h > 0 && d->conv_w > 0 && d->conv_c > 0 &&
-                      d->conv_k > 0 && d->conv_r > 0 && d->conv_s > 0 && d->conv_stride > 0 &&
-                      d->conv_p > 0 && d->conv_q > 0,
-                  "dfu_gemm: conv geometry missing");
-    if (d->a_mode == DFU_OPND_CONV_FWD) {
-      DFU_CHECK_ARG(d->conv_c % BK == 0, "dfu_gemm: implicit conv fwd needs C %% 64 == 0");
-      DFU_CHECK_ARG(d->K == d->conv_r * d->conv_s * d->conv_c, "dfu_gemm: conv fwd K != RSC");
-      DFU_CHECK_ARG(d->M == d->conv_n * d->conv_p * d->conv_q, "dfu_gemm: conv fwd M != NPQ");
-    }
-    if (d->a_mode == DFU_OPND_CONV_DGRAD) {
-      DFU_CHECK_ARG(d->conv_k % BK == 0, "dfu_gemm: conv dgrad needs Kout %% 64 == 0");
-      DFU_CHECK_ARG(d->K == d->conv_r * d->conv_s * d->conv_k, "dfu_gemm: conv dgrad K != RSK");
-      DFU_CHECK_ARG(d->M == d->conv_n * d->conv_h * d->conv_w, "dfu_gemm: conv dgrad M != NHW");
-      DFU_CHECK_ARG(d->conv_c % 8 == 0, "dfu_gemm: conv dgrad needs C %% 8 == 0");
-      DFU_CHECK_ARG(d->b_mode == DFU_OPND_CONV_DGRAD_W, "dfu_gemm: conv dgrad needs DGRAD_W B");
-    }
-    if (d->b_mode == DFU_OPND_CONV_WGRAD_X) {
-      DFU_CHECK_ARG(d->conv_c % 8 == 0, "dfu_gemm: conv wgrad needs C %% 8 == 0");
-      DFU_CHECK_ARG(d->N == d->conv_r * d->conv_s * d->conv_c, "dfu_gemm: conv wgrad N != RSC");
-      DFU_CHECK_ARG(d->K == d->conv_n * d->conv_p * d->conv_q, "dfu_gemm: conv wgrad K != NPQ");
-    }
-  }
+  Plan pl;
+  const int rc = check_desc(d, true, &pl);
+  if (rc != DFU_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (d->a_mode != DFU_OPND_CONV_DGRAD || d->conv_stride == 1) return launch(d, pl, nullptr, s);
 
@@ -538,16 +518,18 @@ extern "C" int dfu_gemm(const dfu_gemm_desc* d, void* stream) {
 
 namespace {
 
-int launch(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, hipStream_t s) {
-  const bool acc_epi = d->epilogue == DFU_EPI_F32_ACC;
-  GemmArgs a;
-  const int TM = kTM[pl.tile], TN = kTN[pl.tile];
+// (gemm_ps.hip: buffer-DMA operand loads, a schedule switch of their own)
+inline bool is_ps(int tile) { return tile == T256x256ps || tile == T192x256ps; }
+
+// The kernel arguments (`ph`: a dgrad stride phase) but a/b_bytes (check_ranges), tail_* (schedule)
+void fill_args(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, GemmArgs& a) {
+  const TileInfo& ti = kTiles[pl.tile];
   a.M = d->M; a.N = d->N; a.K = d->K;
   a.ktiles = cdiv(d->K, BK);
   a.kt_per_split = cdiv(a.ktiles, pl.split);
-  const int splits = cdiv(a.ktiles, a.kt_per_split);
-  a.tiles_m = cdiv(d->M, TM);
-  a.tiles_n = cdiv(d->N, TN);
+  a.split = cdiv(a.ktiles, a.kt_per_split);
+  a.tiles_m = cdiv(d->M, ti.tm);
+  a.tiles_n = cdiv(d->N, ti.tn);
   a.A = (const bf16_t*)d->A; a.lda = d->lda;
   a.B = (const bf16_t*)d->B; a.ldb = d->ldb;
   a.C = d->C; a.ldc = d->ldc;
@@ -556,7 +538,6 @@ int launch(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, hipStream_t 
   a.aux = d->aux; a.ldaux = d->ldaux;
   a.aux_out = d->aux_out; a.ldaux_out = d->ldaux_out;
   a.stats = d->stats;
-  a.split = splits;
   a.n4 = (d->N % 4 == 0 && d->ldc % 4 == 0 && (d->aux == nullptr || d->ldaux % 4 == 0) &&
           (d->aux_out == nullptr || d->ldaux_out % 4 == 0))
              ? 1
@@ -566,21 +547,14 @@ int launch(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, hipStream_t 
              ? 1
              : 0;
   a.slab = nullptr;
-  if (acc_epi && splits > 1 && d->workspace != nullptr &&
-      d->workspace_bytes >= (int64_t)splits * d->M * d->N * 4)
+  if (d->epilogue == DFU_EPI_F32_ACC && a.split > 1 && d->workspace != nullptr &&
+      d->workspace_bytes >= (int64_t)a.split * d->M * d->N * 4)
     a.slab = (float*)d->workspace;
   // in-kernel split-K reduction: the last split of a tile to finish adds the slabs into C
   a.counters = nullptr;
-  if (a.slab != nullptr && g_inkernel_reduce && splits <= 8 && d->tile_counters != nullptr &&
-      d->tile_counters_len >= a.tiles_m * a.tiles_n && pl.tile != T256x256p8 &&
-      pl.tile != T256x256ps && pl.tile != T192x256ps)
+  if (a.slab != nullptr && g_inkernel_reduce && a.split <= 8 && d->tile_counters != nullptr &&
+      d->tile_counters_len >= a.tiles_m * a.tiles_n && !ti.phased)
     a.counters = d->tile_counters;
-  // the phased kernel has neither fp32 atomics nor the in-kernel reduction: split-K needs slabs
-  DFU_CHECK_ARG(!((pl.tile == T256x256p8 || pl.tile == T256x256ps || pl.tile == T192x256ps) &&
-                  acc_epi && splits > 1 &&
-                  a.slab == nullptr),
-                "dfu_gemm: split-K on the phased 256x256 tile needs a workspace "
-                "(dfu_gemm_workspace_bytes)");
   a.ep_tokens = d->ep_tokens;
   a.cn = d->conv_n; a.ch = d->conv_h; a.cw = d->conv_w; a.cc = d->conv_c;
   a.ck = d->conv_k; a.cr = d->conv_r; a.cs = d->conv_s;
@@ -603,18 +577,6 @@ int launch(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, hipStream_t 
   a.dbg = dbg;
   a.m_ld_bound = round8(d->M);
   a.n_ld_bound = round8(d->N);
-  {
-    // operand extents (elements): K-contiguous [MN][ld], MN-major [K][ld]
-    const int64_t ea = d->a_mode == DFU_OPND_MNMAJOR ? (int64_t)(d->K - 1) * d->lda + a.m_ld_bound
-                                                     : (int64_t)(d->M - 1) * d->lda + d->K;
-    const int64_t eb = d->b_mode == DFU_OPND_MNMAJOR ? (int64_t)(d->K - 1) * d->ldb + a.n_ld_bound
-                                                     : (int64_t)(d->N - 1) * d->ldb + d->K;
-    if (pl.tile == T256x256ps || pl.tile == T192x256ps)
-      DFU_CHECK_ARG(2 * ea < kRsrcBytes && 2 * eb < kRsrcBytes,
-                    "dfu_gemm: operands over 2 GiB need another tile than the buffer-DMA 256x256");
-    a.a_bytes = (int)(2 * ea < kRsrcBytes ? 2 * ea : kRsrcBytes);
-    a.b_bytes = (int)(2 * eb < kRsrcBytes ? 2 * eb : kRsrcBytes);
-  }
   if (d->a_mode >= DFU_OPND_CONV_FWD || d->b_mode >= DFU_OPND_CONV_FWD) {
     a.div_pq = make_fastdiv(a.cp * a.cq);
     a.div_q = make_fastdiv(a.cq);
@@ -625,6 +587,21 @@ int launch(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, hipStream_t 
     a.div_s = make_fastdiv(a.cs);
     if (d->b_mode == DFU_OPND_CONV_WGRAD_X) a.n_ld_bound = d->N;
   }
+}
+
+// The 2 GiB buffer ranges: the operands' (GemmArgs::a_bytes, b_bytes: clamped, but for the
+// buffer-DMA tiles, which need them whole) and the epilogue's outputs.
+int check_ranges(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, GemmArgs& a) {
+  // operand extents (elements): K-contiguous [MN][ld], MN-major [K][ld]
+  const int64_t ea = d->a_mode == DFU_OPND_MNMAJOR ? (int64_t)(d->K - 1) * d->lda + round8(d->M)
+                                                   : (int64_t)(d->M - 1) * d->lda + d->K;
+  const int64_t eb = d->b_mode == DFU_OPND_MNMAJOR ? (int64_t)(d->K - 1) * d->ldb + round8(d->N)
+                                                   : (int64_t)(d->N - 1) * d->ldb + d->K;
+  if (is_ps(pl.tile))
+    DFU_CHECK_ARG(2 * ea < kRsrcBytes && 2 * eb < kRsrcBytes,
+                  "dfu_gemm: operands over 2 GiB need another tile than the buffer-DMA 256x256");
+  a.a_bytes = (int)(2 * ea < kRsrcBytes ? 2 * ea : kRsrcBytes);
+  a.b_bytes = (int)(2 * eb < kRsrcBytes ? 2 * eb : kRsrcBytes);
   // the epilogue addresses its outputs by 32-bit offsets within a 2 GiB buffer range
   const bool c32 = d->epilogue == DFU_EPI_F32 || d->epilogue == DFU_EPI_F32_RESID ||
                    d->epilogue == DFU_EPI_F32_ACC || d->epilogue == DFU_EPI_PATCH ||
@@ -634,56 +611,74 @@ int launch(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, hipStream_t 
   if (d->epilogue == DFU_EPI_PATCH && d->ep_tokens > 0)
     c_rows = (int64_t)(d->M / d->ep_tokens) * (d->ep_tokens + 1);
   DFU_CHECK_ARG(c_rows * d->ldc * (c32 ? 4 : 2) < kRsrcBytes &&
-                    (a.slab == nullptr || (int64_t)splits * d->M * d->N * 4 < kRsrcBytes),
+                    (a.slab == nullptr || (int64_t)a.split * d->M * d->N * 4 < kRsrcBytes),
                 "dfu_gemm: output larger than the 2 GiB epilogue buffer range");
-  // Persistent schedule: at most one wave of workgroups (CUs x occupancy), each walking its
-  // work units as one K-step stream; split-K by fp32 atomics (no workspace) keeps one unit
-  // per workgroup (its atomics have no fixed vmcnt count).
-  const int slots = kCUs * kOcc[pl.tile];
+  return DFU_OK;
+}
+
+// Tail split (GemmArgs::tail_*) and schedule; returns the workgroups to launch: one per work
+// unit, or persistent, at most one wave (CUs x occupancy).  Split-K by fp32 atomics (no
+// workspace) keeps one unit per workgroup (its atomics have no fixed vmcnt count).
+int schedule(const dfu_gemm_desc* d, const Plan& pl, GemmArgs& a) {
   a.tail_full = a.tail_r = a.tail_s = a.tail_kps = 0;
   a.tslab = nullptr;
-  if (!acc_epi && splits == 1 && kTailOK[pl.tile]) {
-    const Tail t =
-        tail_plan(a.tiles_m * a.tiles_n, slots, a.ktiles, TM, TN, kStepUs[kBase[pl.tile]]);
-    if (t.r > 0 && d->workspace != nullptr && d->workspace_bytes >= t.bytes &&
-        d->tile_counters != nullptr && d->tile_counters_len >= t.r) {
-      a.tail_full = t.full; a.tail_r = t.r; a.tail_s = t.s; a.tail_kps = t.kps;
-      a.tslab = (float*)d->workspace;
-      a.counters = d->tile_counters;
-    }
+  const Tail t = tail_plan(d, pl);
+  if (t.r > 0 && d->workspace != nullptr && d->workspace_bytes >= t.bytes &&
+      d->tile_counters != nullptr && d->tile_counters_len >= t.r) {
+    a.tail_full = t.full; a.tail_r = t.r; a.tail_s = t.s; a.tail_kps = t.kps;
+    a.tslab = (float*)d->workspace;
+    a.counters = d->tile_counters;
   }
-  const int units = a.tail_r ? a.tail_full + a.tail_r * a.tail_s : a.tiles_m * a.tiles_n * splits;
-  const bool atomics = acc_epi && splits > 1 && a.slab == nullptr;
-  const bool pers = (pl.tile == T256x256ps || pl.tile == T192x256ps) ? g_persistent_ps
-                                                                     : g_persistent;
-  const int nwg = (pers && !atomics && units > slots) ? slots : units;
+  const int units = a.tail_r ? a.tail_full + a.tail_r * a.tail_s : a.tiles_m * a.tiles_n * a.split;
+  const bool atomics = d->epilogue == DFU_EPI_F32_ACC && a.split > 1 && a.slab == nullptr;
+  const bool pers = is_ps(pl.tile) ? g_persistent_ps : g_persistent;
+  const int slots = kTiles[pl.tile].slots();
+  return (pers && !atomics && units > slots) ? slots : units;
+}
+
+// Adds the split-K slabs of a finished launch into C.
+int reduce_slabs(const dfu_gemm_desc* d, const GemmArgs& a, hipStream_t s) {
+  const int splits = a.split;
+  const int64_t n = (int64_t)d->M * d->N;
+  const bool vec = d->N % 4 == 0 && d->ldc % 4 == 0 && ((uintptr_t)d->C & 15) == 0;
+  int64_t blocks = (vec ? n / 4 : n) / 256 + 1;
+  if (blocks > 8192) blocks = 8192;
+  if (blocks < kCUs && splits >= 8 && g_wide_reduce) {
+    // too few elements to fill the chip one lane each: split the slabs over waves too
+    const int nw = splits < 16 ? splits : 16;
+    const int64_t units = vec ? n / 4 : n;
+    const unsigned wb = (unsigned)((units + 63) / 64);
+    if (vec)
+      hipLaunchKernelGGL(k_splitk_reduce_wide<true>, dim3(wb), dim3(64 * nw), 0, s, a.slab,
+                         splits, d->M, d->N, (float*)d->C, d->ldc);
+    else
+      hipLaunchKernelGGL(k_splitk_reduce_wide<false>, dim3(wb), dim3(64 * nw), 0, s, a.slab,
+                         splits, d->M, d->N, (float*)d->C, d->ldc);
+  } else if (vec)
+    hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)blocks), dim3(256), 0, s, a.slab, splits,
+                       d->M, d->N, (float*)d->C, d->ldc);
+  else
+    hipLaunchKernelGGL(k_splitk_reduce_scalar,
+                       dim3((unsigned)((d->N + 255) / 256), (unsigned)(d->M < 4096 ? d->M : 4096)),
+                       dim3(256), 0, s, a.slab, splits, d->M, d->N, (float*)d->C, d->ldc);
+  DFU_LAUNCH_CHECK();
+  return DFU_OK;
+}
+
+int launch(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, hipStream_t s) {
+  GemmArgs a;
+  fill_args(d, pl, ph, a);
+  // the phased kernel has neither fp32 atomics nor the in-kernel reduction: split-K needs slabs
+  DFU_CHECK_ARG(!(kTiles[pl.tile].phased && d->epilogue == DFU_EPI_F32_ACC && a.split > 1 &&
+                  a.slab == nullptr),
+                "dfu_gemm: split-K on the phased 256x256 tile needs a workspace "
+                "(dfu_gemm_workspace_bytes)");
+  const int rc = check_ranges(d, pl, ph, a);
+  if (rc != DFU_OK) return rc;
+  const int nwg = schedule(d, pl, a);
   hipLaunchKernelGGL(pl.entry->fn, dim3(nwg), dim3(pl.entry->threads), 0, s, a);
   DFU_LAUNCH_CHECK();
-  if (a.slab != nullptr && a.counters == nullptr) {
-    const int64_t n = (int64_t)d->M * d->N;
-    const bool vec = d->N % 4 == 0 && d->ldc % 4 == 0 && ((uintptr_t)d->C & 15) == 0;
-    int64_t blocks = (vec ? n / 4 : n) / 256 + 1;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < kCUs && splits >= 8 && g_wide_reduce) {
-      // too few elements to fill the chip one lane each: split the slabs over waves too
-      const int nw = splits < 16 ? splits : 16;
-      const int64_t units = vec ? n / 4 : n;
-      const unsigned wb = (unsigned)((units + 63) / 64);
-      if (vec)
-        hipLaunchKernelGGL(k_splitk_reduce_wide<true>, dim3(wb), dim3(64 * nw), 0, s, a.slab,
-                           splits, d->M, d->N, (float*)d->C, d->ldc);
-      else
-        hipLaunchKernelGGL(k_splitk_reduce_wide<false>, dim3(wb), dim3(64 * nw), 0, s, a.slab,
-                           splits, d->M, d->N, (float*)d->C, d->ldc);
-    } else if (vec)
-      hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)blocks), dim3(256), 0, s, a.slab, splits,
-                         d->M, d->N, (float*)d->C, d->ldc);
-    else
-      hipLaunchKernelGGL(k_splitk_reduce_scalar,
-                         dim3((unsigned)((d->N + 255) / 256), (unsigned)(d->M < 4096 ? d->M : 4096)),
-                         dim3(256), 0, s, a.slab, splits, d->M, d->N, (float*)d->C, d->ldc);
-    DFU_LAUNCH_CHECK();
-  }
+  if (a.slab != nullptr && a.counters == nullptr) return reduce_slabs(d, a, s);
   return DFU_OK;
 }
 

@@ -1,8 +1,35 @@
-// Dispatch-table entries of the GEMM template, one table per tile shape (gemm_t*.hip).
+// The GEMM tile table: one row per tile shape (DFU_TILES), the only source of tile facts, and
+// the dispatch entries of each tile's kernels (gemm_t*.hip, gemm_p8.hip, gemm_ps.hip).
 #pragma once
+#ifdef __HIP__  // the kernels, for the entry macros below (plain C++ reads the table alone)
 #include "gemm_kernel.h"
+#endif
+
+// X(name, TM, TN, workgroups per CU, phased, tail-split, step_us, round_us) in tile-id order:
+// id = row + 1 is ABI (dfu_gemm_desc.tile, gemm_tuned.inc; Python: ops.TILES).
+// phased: the phase-scheduled kernels (gemm_p8.hip, gemm_ps.hip): no split-pair A, no fp32
+// atomics, no in-kernel split-K reduction.  tail-split: Tail in gemm.hip.
+// step_us / round_us, the wave-quantisation cost model: a launch takes ceil(tiles * splits /
+// (256 CUs * workgroups per CU)) rounds, each costing round_us (prologue fill + epilogue) +
+// k-steps * step_us.  Fitted on MI355X to tools/gemm_bench.py --sweep (ViT qkv K=768 vs fc2
+// K=3072 forward rows, r01).  At 2 per CU two co-resident workgroups share the MFMA pipe (step
+// cost ~doubles) but hide each other's fill and epilogue.  The phased and the 64-column tiles
+// are priced high: only the offline-tuned table or a tile hint selects them.
+#define DFU_TILES(X)                                                                   \
+  X(128x128, 128, 128, 1, false, true, 0.57, 4.8)                                      \
+  X(256x128, 256, 128, 1, false, false, 0.89, 8.3)                                     \
+  X(128x256, 128, 256, 1, false, false, 0.90, 7.4)                                     \
+  X(256x256, 256, 256, 1, false, false, 1.41, 13.9)                                    \
+  X(128x128o2, 128, 128, 2, false, true, 0.70, 6.1)                                    \
+  X(128x128w4, 128, 128, 2, false, false, 0.65, 6.1) /* 4 waves */                     \
+  X(256x256p8, 256, 256, 1, true, false, 3.0, 20.0)  /* K-contiguous A and B only */   \
+  X(256x256ps, 256, 256, 1, true, false, 3.0, 20.0)  /* persistent */                  \
+  X(192x256ps, 192, 256, 1, true, false, 3.0, 20.0)  /* persistent, K-contiguous A */  \
+  X(256x64, 256, 64, 1, false, false, 3.0, 20.0)     /* 4 waves, K-contiguous B */     \
+  X(128x64o2, 128, 64, 2, false, false, 3.0, 20.0)   /* 4 waves, K-contiguous B */
 
 namespace dfu {
+struct GemmArgs;
 typedef void (*gemm_fn)(const GemmArgs);
 // Entry.e of an fp16-operand kernel (dfu_gemm_desc.operand_type 1): the epilogue | kF16Key
 constexpr int kF16Key = 64;
@@ -14,37 +41,15 @@ struct Entry {
   int lds_bytes;
   int threads;
 };
-enum TileId {
-  T128x128 = 0, T256x128 = 1, T128x256 = 2, T256x256 = 3, T128x128o2 = 4, T128x128w4 = 5,
-  T256x256p8 = 6,  // phased 256x256 (gemm_p8.hip): K-contiguous A and B only
-  T256x256ps = 7,  // persistent phased 256x256 (gemm_ps.hip)
-  T192x256ps = 8,  // persistent phased 192x256 (gemm_ps.hip): K-contiguous A
-  T256x64 = 9,     // 4-wave 256x64 (64-channel convs; K-contiguous B)
-  T128x64o2 = 10,  // 4-wave 128x64 at 2 workgroups per CU
-  NTILES = 11
-};
-extern const Entry kTable128x128[];
-extern const int kTable128x128N;
-extern const Entry kTable256x128[];
-extern const int kTable256x128N;
-extern const Entry kTable128x256[];
-extern const int kTable128x256N;
-extern const Entry kTable256x256[];
-extern const int kTable256x256N;
-extern const Entry kTable128x128o2[];
-extern const int kTable128x128o2N;
-extern const Entry kTable128x128w4[];
-extern const int kTable128x128w4N;
-extern const Entry kTable256x256p8[];
-extern const int kTable256x256p8N;
-extern const Entry kTable256x256ps[];
-extern const int kTable256x256psN;
-extern const Entry kTable192x256ps[];
-extern const int kTable192x256psN;
-extern const Entry kTable256x64[];
-extern const int kTable256x64N;
-extern const Entry kTable128x64o2[];
-extern const int kTable128x64o2N;
+#define X(name, ...) T##name,
+enum TileId { DFU_TILES(X) NTILES };
+#undef X
+// a tile's kernels, kTable<name>[kTable<name>N]: defined next to their instantiations
+#define X(name, ...)                   \
+  extern const Entry kTable##name[]; \
+  extern const int kTable##name##N;
+DFU_TILES(X)
+#undef X
 }  // namespace dfu
 
 #define DFU_ENTRY(A, B, E, TMv, TNv, TID)                                             \

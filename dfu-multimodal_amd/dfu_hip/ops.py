@@ -314,7 +314,7 @@ def gemm_workspace_bytes(M, N, K, a_mode, b_mode, epilogue=L.EPI_F32_ACC, split_
 
 
 def gemm_plan(M, N, K, a_mode, b_mode, epilogue, split_k=0, tile=0):
-    """(tile id 1..4, split-K) the library's cost model picks."""
+    """(tile id as in TILES, split-K) the library plans for this descriptor."""
     d = _plan_desc(M, N, K, a_mode, b_mode, epilogue, split_k, tile)
     t, sk = ctypes.c_int32(), ctypes.c_int32()
     check(lib().dfu_gemm_plan(ctypes.byref(d), ctypes.byref(t), ctypes.byref(sk)), "dfu_gemm_plan")

@@ -162,12 +162,14 @@ int dfu_gemm_stats_tiles(int32_t M);
 /* Workspace bytes for this descriptor: deterministic split-K slabs (F32_ACC) or tail-split
  * slabs (other epilogues); 0 if the launch needs none. */
 int64_t dfu_gemm_workspace_bytes(const dfu_gemm_desc* desc);
-/* The tile (1..11, as dfu_gemm_desc.tile) and split-K the cost model picks for this descriptor. */
+/* The tile (1..11, as dfu_gemm_desc.tile) and split-K dfu_gemm runs this descriptor with (the
+ * offline-tuned table, else the cost model). */
 int dfu_gemm_plan(const dfu_gemm_desc* desc, int32_t* tile, int32_t* split_k);
 /* GEMM schedule switch (tests, A/B timing), a bit mask: bit 0 the generic tiles, bit 1 the
  * persistent phased 256-wide tiles; set = persistent workgroups, each walking several work units
  * as one continuous K-step stream; clear = one workgroup per work unit.  Default 2 (round 6).
- * Every setting gives bitwise-identical results.  Returns the previous mask. */
+ * Every setting gives bitwise-identical results: the plan (dfu_gemm_plan,
+ * dfu_gemm_workspace_bytes) does not depend on the mask.  Returns the previous mask. */
 int dfu_gemm_set_persistent(int32_t mode);
 /* Split-K reduction switch: 1 = inside the GEMM when the descriptor carries tile
  * counters, 0 (default: measured faster) = the separate reduce kernel.  Bitwise-identical; returns the

@@ -130,6 +130,29 @@ def test_gemm_persistent_bitwise(M, N, K, epi, tile):
         assert (res[0][0] - ref).abs().max().item() < 3e-3 * math.sqrt(K)
 
 
+def test_auto_split_k_same_under_both_schedules():
+    """An F32_ACC launch on the automatic plan (split_k = 0, tile = 0) whose split-K the cost
+    model chose by the schedule switch while it priced the persistent schedule (2 ways at mode 0,
+    5 at mode 1: tools/gemm_plan_snapshot.py SCHEDULE_SENSITIVE): the plan, and so the summation
+    order, is now the same under both schedules."""
+    M, N, K = 1949, 1292, 8000
+    m8, n8 = (M + 7) // 8 * 8, (N + 7) // 8 * 8
+    Akm = drnd(K, m8, seed=51)
+    Bkn = drnd(K, n8, seed=52)
+    r32 = drnd(M, N, dtype=torch.float32, seed=53)
+
+    def run():
+        C = r32.clone()
+        ops.gemm(M, N, K, Akm, m8, Bkn, n8, C, N, a_mode=L.OPND_MNMAJOR, b_mode=L.OPND_MNMAJOR,
+                 epilogue=L.EPI_F32_ACC, split_k=0, tile=0)
+        return [C]
+
+    res = both_schedules(run)
+    assert_bitwise(res, f"auto split-K acc {M}x{N}x{K}")
+    ref = r32 + Akm.float()[:, :M].t() @ Bkn.float()[:, :N]
+    assert (res[0][0] - ref).abs().max().item() < 3e-3 * math.sqrt(K)
+
+
 CONV = [  # N, H, W, C, K, R, S, stride, pad — ResNet-50 layers at B = 64
     (64, 56, 56, 64, 64, 3, 3, 1, 1),
     (64, 28, 28, 128, 128, 3, 3, 2, 1),

@@ -115,6 +115,35 @@ def test_gemm_planner_workspace():
                                     epilogue=L.EPI_BF16) == 0
 
 
+def test_gemm_plans_match_snapshot_under_every_schedule():
+    """Every case of tests/golden/gemm_plans.json (tools/gemm_plan_snapshot.py: recorded from the
+    commit before the dispatch refactor, at the default schedule) plans to the recorded return
+    code, tile, split-K and workspace bytes (with and without the tail split) -- under each
+    dfu_gemm_set_persistent mode: the schedule switch does not reach the planner."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location(
+        "gemm_plan_snapshot", os.path.join(REPO, "tools", "gemm_plan_snapshot.py"))
+    snap = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(snap)
+    with open(os.path.join(REPO, "tests", "golden", "gemm_plans.json")) as f:
+        fix = json.load(f)
+    assert (fix["linear"], fix["conv"], fix["result"]) == (snap.LINEAR, snap.CONV, snap.RESULT)
+    nres = len(snap.RESULT)
+    assert len(fix["cases"]) > 1500
+    assert [tuple(c[:3]) for c in fix["cases"][-2:]] == snap.SCHEDULE_SENSITIVE
+    lib = L.load()
+    for mode in (0, 1, 2, 3):
+        old = lib.dfu_gemm_set_persistent(mode)
+        try:
+            bad = [(c[:-nres], c[-nres:], got) for c in fix["cases"]
+                   for got in [snap.answers(lib, c[:-nres])] if got != c[-nres:]]
+        finally:
+            lib.dfu_gemm_set_persistent(old)
+        assert not bad, f"persistent mode {mode}: {len(bad)} plans moved (case, recorded, got), " \
+                        f"first: {bad[:3]}"
+
+
 @pytest.mark.parametrize("M,tiles", [(1, 1), (128, 1), (129, 2), (200704, 1568), (3136, 25)])
 def test_stats_tiles_are_128_row_blocks(M, tiles):
     assert ops.stats_tiles(M) == tiles

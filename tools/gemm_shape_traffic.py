@@ -16,13 +16,17 @@ run; its per-shape times replace the ones recorded in shapes.json, which were ta
 import collections
 import csv
 import json
+import os
 import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "dfu-multimodal_amd")]
+from dfu_hip import ops  # noqa: E402
 
 OPND = ["KM", "MN", "CFWD", "CDGD", "CDGW", "CWGX"]
 EPI = ["BF16", "RELU", "GELU", "F32", "RESID", "DGELU", "ADD", "ACC", "ACCW", "STATS", "PATCH",
        "F32STATS", "DSTATS", "X3GELU", "F16DUAL", "F16GELU"]
-TILE = ["auto", "128x128", "256x128", "128x256", "256x256", "128x128o2", "128x128w4", "256x256p8",
-        "256x256ps", "192x256ps", "256x64", "128x64o2"]
+TILE = list(ops.TILES)  # in id order
 
 
 def segments(path, counter):
