@@ -441,9 +441,11 @@ int dfu_ce_weighted_fwd(const float* logits, const int64_t* labels, const float*
 int dfu_ce_weighted_bwd(const float* dlogits_saved, const float* grad_loss, int32_t B,
                         int32_t C, float* dlogits, void* stream);
 /* torch.optim.AdamW (lr, betas, eps, weight_decay) over a table of tensors
- * (train_multimodal_fusion.py:347,380).  step_dev is an int64 device counter incremented by
- * the launch (graph-capturable bias correction).  Tensors are described by device arrays of
- * pointers and element counts. */
+ * (train_multimodal_fusion.py:347,380).  step_dev is an int64 device counter the launch READS
+ * (graph-capturable bias correction; dfu_step_increment advances it before the launch).
+ * Tensors are described by device arrays of pointers (a NULL grad is a zero gradient) and
+ * element counts; chunk_offsets[c] = (tensor index << 32) | chunk index within that tensor,
+ * chunks of 65536 elements, one entry per chunk of every tensor. */
 int dfu_adamw(float* const* params, float* const* grads, float* const* exp_avg,
               float* const* exp_avg_sq, const int64_t* numels, int32_t ntensors,
               const int64_t* chunk_offsets, int32_t nchunks, float lr, float beta1,

@@ -92,10 +92,37 @@ CHILD = textwrap.dedent(r'''
         r["replay_equal"] = bool(torch.equal(C2, ref2))
     res["cold_stream_counters"] = r
 
+    # 5. non-library work the step leaves on the encoder side stream (Fn.side_stream, a library
+    #    stream: try_capture knows it without having seen a launch there) is joined into the
+    #    capture, and every replay performs it
+    from dfu_hip import functional as Fn
+    side = Fn.side_stream(DEV)   # made before the capture: creating a stream is not capturable
+    scratch = torch.zeros(1024, device=DEV)
+
+    def step5():
+        C1.zero_()
+        wgrad(C1)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            scratch.add_(1.0)    # torch's own kernel, not joined by the step itself
+    step5()
+    torch.cuda.synchronize()
+    msgs = []
+    g = graphs.try_capture(step5, log=msgs.append)
+    r = dict(captured=g is not None, log=msgs)
+    if g is not None:
+        torch.cuda.synchronize()
+        scratch.zero_()
+        C1.fill_(7.0)
+        g.replay()
+        g.replay()
+        torch.cuda.synchronize()
+        r["side_work_replayed_twice"] = bool(torch.equal(scratch, torch.full_like(scratch, 2.0)))
+        r["origin_work_replayed"] = bool(torch.equal(C1, ref1))
+    res["unjoined_side_stream"] = r
+
     # 4. a library stream first created inside the capture (hipStreamCreate is not capturable):
     #    refused with DfuError before the call, the capture ends cleanly, eager fallback
-    from dfu_hip import functional as Fn
-
     def step4():
         ws = Fn.wgrad_stream(torch.device(DEV))
         ws.wait_stream(torch.cuda.current_stream())
@@ -153,6 +180,9 @@ def test_capture_fork_onto_plain_torch_stream():
     assert r1["captured"] and r1["replay_equal"], r1
     r2 = res["cold_stream_counters"]
     assert r2["captured"] and r2["eager_equal"] and r2["replay_equal"], r2
+    r5 = res["unjoined_side_stream"]
+    assert r5["captured"] and not r5["log"], r5
+    assert r5["side_work_replayed_twice"] and r5["origin_work_replayed"], r5
     r4 = res["stream_created_in_capture"]
     assert not r4["captured"] and r4["eager_equal"], r4
     assert any("DfuError" in m and "inside a HIP-graph capture" in m for m in r4["log"]), r4

@@ -1,5 +1,8 @@
-"""Per-kernel numerics on the GPU: every libdfu_hip entry point against a plain PyTorch fp32
-reference of the same op on the same (bf16-representable) inputs."""
+"""Per-kernel numerics on the GPU: the GEMM, convolution, attention, normalisation, pooling,
+layout, loss and optimizer entry points of libdfu_hip against a plain PyTorch fp32 reference of
+the same op on the same (bf16-representable) inputs.  The remaining exports are tested directly
+in test_entrypoints_gpu.py, the other code paths of the kernels here in
+test_kernel_edges_gpu.py; test_export_coverage_cpu.py checks that no export is left out."""
 import math
 
 import pytest
