@@ -28,6 +28,10 @@ import torch
 
 from . import _lib as L
 from . import ops
+# stream state lives in dfu_hip.streams; the stream accessors stay known by Fn.<name>
+from .streams import (current_stream, join_grad_streams, new_stream, on_stream,  # noqa: F401
+                      side_stream, stream_wait, wgrad_stream)
+from .streams import grad_streams as _grad_streams  # grad_buffer stores into it directly
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -131,12 +135,6 @@ def remove_grad_ready_hook(fn):
         _grad_ready_hooks.remove(fn)
 
 
-# Streams that wrote persistent parameter gradients since the last join.  Autograd synchronises
-# only the gradients it returns; these buffers are written in place (possibly on a branch's side
-# stream, see models.fusion), so consumers (FusedAdamW.step, GradAllReducer.finish) join first.
-_grad_streams = {}
-
-
 def grad_buffer(p):
     """Persistent fp32 gradient buffer of parameter p (zeroed on first use); notes the current
     stream as a gradient producer."""
@@ -156,22 +154,9 @@ def grad_buffer(p):
 
 
 def _current_stream_obj(t):
-    """The current stream of t's device as one cached torch Stream object (ops.current_stream;
-    called for every parameter gradient of the step)."""
-    return ops.current_stream(t.get_device())
-
-
-def join_grad_streams(stream=None, clear=True):
-    """Make `stream` (default: the current stream) wait for every stream that wrote parameter
-    gradients since the last clearing join."""
-    if not _grad_streams:
-        return
-    cur = stream if stream is not None else ops.current_stream()
-    for st in _grad_streams.values():
-        if st != cur:
-            ops.stream_wait(cur, st)
-    if clear:
-        _grad_streams.clear()
+    """The current stream of t's device as one cached torch Stream object
+    (streams.current_stream; called for every parameter gradient of the step)."""
+    return current_stream(t.get_device())
 
 
 # Parameter gradients are written in place, possibly on a branch's side stream or the ViT
@@ -202,7 +187,7 @@ def remove_backward_end_hook(fn):
 def arm_backward_join():
     if _join_armed[0] or not torch.cuda.is_available():
         return
-    target = ops.current_stream()
+    target = current_stream()
     _join_armed[0] = True
 
     def _join():
@@ -214,6 +199,11 @@ def arm_backward_join():
         torch.autograd.Variable._execution_engine.queue_callback(_join)
     except RuntimeError:  # not inside a backward pass (a direct .backward() call of a Function)
         _join_armed[0] = False
+
+
+def disarm_backward_join():
+    """Forget an armed join whose backward pass a failed graph capture cut short."""
+    _join_armed[0] = False
 
 
 def _optimizer_pre_hook(optimizer, args, kwargs):
@@ -228,55 +218,8 @@ except ImportError:  # torch without global optimizer hooks
     pass
 
 
-_side_streams = {}
-# Every library stream runs at the default HIP priority: a high-priority ViT side stream gained
-# 0.3% in the eager fusion step, but a C5 Grad-CAM step whose warm-up ran with it replayed from
-# a HIP graph at 49.6-54.4 ms against 22.9 ms (round 3).
-
-
-def new_stream(idx, priority=0):
-    """A library-owned non-blocking HIP stream (dfu_stream_create) as a torch ExternalStream.
-    Never returned to torch's stream pool: a stream a failed graph capture left capturing is
-    retired (dfu_hip.graphs) and this makes a fresh one."""
-    import ctypes
-    # hipStreamCreate is not a capturable call: under a global-mode capture it invalidates the
-    # capture of every stream forked into it (dfu_hip.graphs)
-    ops.refuse_in_capture("a new library stream")
-    h = ctypes.c_void_p(0)
-    with torch.cuda.device(idx):
-        L.check(L.load().dfu_stream_create(int(priority), ctypes.byref(h)), "dfu_stream_create")
-    return torch.cuda.ExternalStream(h.value, device=torch.device("cuda", idx))
-
-
-def side_stream(device):
-    """One persistent side stream per device for the concurrent encoder branch."""
-    idx = torch.device(device).index
-    if idx is None:
-        idx = torch.cuda.current_device()
-    st = _side_streams.get(idx)
-    if st is None:
-        st = _side_streams[idx] = new_stream(idx)
-    return st
-
-
-_wgrad_streams = {}
 # DFU_VIT_WGRAD_STREAM=0: the ViT weight-gradient GEMMs stay on the backward's own stream (A/B)
 _VIT_WGRAD_STREAM = os.environ.get("DFU_VIT_WGRAD_STREAM", "1") != "0"
-
-
-def wgrad_stream(device):
-    """One persistent stream per device for the ViT blocks' weight-gradient GEMMs: they depend
-    only on tensors already produced and feed only the optimizer, so they run beside the input-
-    gradient chain, whose N = 768 GEMMs fill 150 of the 256 CUs (12608 / 256 x 768 / 256 tiles)
-    and whose LayerNorm / attention kernels leave the MFMAs idle."""
-    idx = torch.device(device).index
-    if idx is None:
-        idx = torch.cuda.current_device()
-    st = _wgrad_streams.get(idx)
-    if st is None:
-        st = _wgrad_streams[idx] = new_stream(idx)
-    return st
-
 
 _concurrent_encoders = [0]
 
@@ -301,13 +244,13 @@ class _Beside:
 
     def __init__(self, stream):
         self.ws = stream
-        self.cur = ops.current_stream() if stream is not None else None
+        self.cur = current_stream() if stream is not None else None
 
     def run(self, fn, *tensors):
         if self.ws is None:
             return fn()
-        ops.stream_wait(self.ws, self.cur)
-        with ops.on_stream(self.ws):
+        stream_wait(self.ws, self.cur)
+        with on_stream(self.ws):
             for t in tensors:
                 t.record_stream(self.ws)
             return fn()
@@ -333,7 +276,7 @@ def module_param(mod, name):
     return b[name] if name in b else getattr(mod, name)
 
 
-def _wants(p):
+def wants(p):
     return p is not None and p.requires_grad
 
 
@@ -360,7 +303,7 @@ def from_rows(r, B, H, W, C):
     return r.view(B, H, W, C).permute(0, 3, 1, 2)
 
 
-def _krsc_strided(w):
+def krsc_strided(w):
     """A 4-D OIHW-shaped tensor whose memory is KRSC (channels-last), as optim.FlatParams
     stores spatial conv weights."""
     return (w.dim() == 4 and not w.is_contiguous()
@@ -369,7 +312,7 @@ def _krsc_strided(w):
 
 def _rows2d(w):
     """[N, K] rows of w in its storage order (KRSC for a channels-last conv weight: a view)."""
-    if _krsc_strided(w):
+    if krsc_strided(w):
         return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)
     return w.reshape(w.shape[0], -1)
 
@@ -437,7 +380,7 @@ def conv_weight_flipped(w):
     """W'[C][R][S][K] = W[K][R-1-r][S-1-s][C] (bf16, [C][R*S*K]) of a FusedAdamW-managed
     channels-last conv weight, or None.  Re-derived (one launch, on the current stream) on the
     first use after the optimizer rewrote the shadows or the weight was edited outside it."""
-    if not _DGRAD_FLIP or not _krsc_strided(w):
+    if not _DGRAD_FLIP or not krsc_strided(w):
         return None
     sh = weight_bf16_rows(w)
     flat = getattr(w, "_dfu_flat", None)
@@ -471,7 +414,7 @@ def conv1x1_weight_T(conv, geom):
 def conv_weight_bf16(w):
     """fp32 OIHW conv weight -> bf16 KRSC GEMM operand: the shadow view for a 1x1 conv (OIHW ==
     KRSC) and for a FusedAdamW-managed weight stored channels-last; else a packing kernel."""
-    if (w.shape[2] == 1 and w.shape[3] == 1) or _krsc_strided(w):
+    if (w.shape[2] == 1 and w.shape[3] == 1) or krsc_strided(w):
         return weight_bf16_rows(w)
     return ops.pack_conv_weight(w.detach())
 
@@ -529,7 +472,7 @@ def _take_x3(x):
 
 
 # ---------------------------------------------------------------------- BatchNorm helper
-class _BN:
+class BNState:
     """Forward/backward state of one BatchNorm2d applied to a GEMM output with stats."""
 
     def __init__(self, bn, M, C, device):
@@ -564,8 +507,8 @@ class _BN:
         `out` is not read); or 3 (`out` is the forward's ReLU bitmask, ops.bn_apply(mask=))."""
         bn = self.bn
         w, b = module_param(bn, "weight"), module_param(bn, "bias")
-        dgamma = grad_buffer(w) if _wants(w) else None
-        dbeta = grad_buffer(b) if _wants(b) else None
+        dgamma = grad_buffer(w) if wants(w) else None
+        dbeta = grad_buffer(b) if wants(b) else None
         ops.bn_bwd(dout, y, out, relu, self.mean, self.invstd, w, self.M, self.C, dy,
                    dres, dgamma, dbeta, batch_stats=self.training, scale=self.scale,
                    shift=self.shift)
@@ -648,7 +591,7 @@ def conv_wgrad(dy_rows, x_rows, geom, dw):
     if g.r == 1 and g.s == 1 and g.stride == 1 and g.pad == 0:
         ops.gemm(g.k, g.c, M, dy_rows, g.k, x_rows, g.c, dw, g.c, a_mode=L.OPND_MNMAJOR,
                  b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
-    elif _krsc_strided(dw):
+    elif krsc_strided(dw):
         N = g.r * g.s * g.c
         ops.gemm(g.k, N, M, dy_rows, g.k, x_rows, 0, _rows2d(dw), N, a_mode=L.OPND_MNMAJOR,
                  b_mode=L.OPND_CONV_WGRAD_X, epilogue=L.EPI_F32_ACC, conv=g)
@@ -700,7 +643,7 @@ class StemFn(torch.autograd.Function):
         if not fused:
             y = _empty((M, Cout), BF16, x.device)
             stats = _empty((ops.stats_tiles(M), 2, Cout), F32, x.device)
-        bns = _BN(bn, M, Cout, x.device)
+        bns = BNState(bn, M, Cout, x.device)
         if x3:
             a = _empty((M * Cout // 8,), torch.uint8, x.device)  # bn1's ReLU bitmask
             if not fused:
@@ -754,7 +697,7 @@ class StemFn(torch.autograd.Function):
         else:
             ctx.bns.backward(da, y, None, 2, dy, None)
         w = mod.conv1.weight
-        if _wants(w):
+        if wants(w):
             dw = grad_buffer(w).view(Cout, -1)
             K = C * R * S
             if ctx.fused:  # from x itself (the saved tensor is xf): no im2col rows
@@ -812,7 +755,7 @@ class BottleneckFn(torch.autograd.Function):
             y = _empty((M, geom.k), BF16, dev)
             stats = _empty((ops.stats_tiles(M), 2, geom.k), F32, dev)
             conv_fwd(xrows, geom, w, y, stats)
-            st = _BN(bnmod, M, geom.k, dev)
+            st = BNState(bnmod, M, geom.k, dev)
             st.forward_coeffs(stats)
             out = _empty((M, geom.k), BF16, dev)
             ops.bn_apply(y, st.scale, st.shift, residual, relu, out, M, geom.k, mask=mask)
@@ -828,7 +771,7 @@ class BottleneckFn(torch.autograd.Function):
             y_lo = _empty((M, geom.k), BF16, dev)
             stats = _empty((ops.stats_tiles(M), 2, geom.k), F32, dev)
             conv_fwd_x3(xpair, geom, w3x, y, stats, y_lo=y_lo)
-            st = _BN(bnmod, M, geom.k, dev)
+            st = BNState(bnmod, M, geom.k, dev)
             st.forward_coeffs(stats)
             out = _empty((M, geom.k), BF16, dev) if want_pair else None
             lo = _empty((M, geom.k), BF16, dev) if want_pair else None
@@ -914,7 +857,7 @@ class BottleneckFn(torch.autograd.Function):
         M1, M2 = y1.shape[0], y3.shape[0]
 
         def wgrad(conv, dy, x, geom):
-            if _wants(conv.weight):
+            if wants(conv.weight):
                 conv_wgrad(dy, x, geom, grad_buffer(conv.weight))
                 grads_done(conv.weight)
 
@@ -1029,10 +972,10 @@ class PatchEmbedFn(torch.autograd.Function):
         B, T, D, K, C, H, W, ps = ctx.dims
         gX = gX.contiguous()
         gpatch = ops.vit_embed_bwd(gX, B, T + 1, D,
-                                   grad_buffer(cls) if _wants(cls) else None,
-                                   grad_buffer(pos) if _wants(pos) else None,
-                                   grad_buffer(b) if _wants(b) else None)
-        if _wants(w):
+                                   grad_buffer(cls) if wants(cls) else None,
+                                   grad_buffer(pos) if wants(pos) else None,
+                                   grad_buffer(b) if wants(b) else None)
+        if wants(w):
             dw = grad_buffer(w).view(D, K)
             ops.gemm(D, K, B * T, gpatch, D, patches, patches.stride(0), dw, K,
                      a_mode=L.OPND_MNMAJOR, b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
@@ -1068,8 +1011,8 @@ def _ln_bwd(dy_bf, x2d, mean, rstd, norm, rows, D, g, g_bf, gsum=False, batch=No
     """LayerNorm backward; dgamma / dbeta reductions go to `batch` (a PartialReductions) when
     given (the caller reports the parameters done after flushing it)."""
     gsp = ops.layernorm_bwd(dy_bf, D, True, x2d, D, mean, rstd, norm.weight, rows, D, g, D, g_bf,
-                            grad_buffer(norm.weight) if _wants(norm.weight) else None,
-                            grad_buffer(norm.bias) if _wants(norm.bias) else None, gsum=gsum,
+                            grad_buffer(norm.weight) if wants(norm.weight) else None,
+                            grad_buffer(norm.bias) if wants(norm.bias) else None, gsum=gsum,
                             batch=batch)
     if batch is None:
         grads_done(norm.weight, norm.bias)
@@ -1355,16 +1298,16 @@ class ViTBlockFn(torch.autograd.Function):
         # (only when some weight gradient is wanted: a fork with no work -- Grad-CAM's backward
         # through frozen weights -- would leave the stream unjoined, which a graph capture
         # rejects; the streams that wrote gradients are joined by join_grad_streams)
-        wants_w = any(_wants(lin.weight) or _wants(lin.bias)
+        wants_w = any(wants(lin.weight) or wants(lin.bias)
                       for lin in (fc1_l, fc2_l, qkv_l, proj_l))
         bw = _Beside(wgrad_stream(dev) if (ctx.beside and g.is_cuda and wants_w) else None)
         red_w = ops.PartialReductions() if bw.ws is not None else red
 
         def wgrad(lin, dy, x, width=None, partial=None):
             def fn():
-                if _wants(lin.weight):
+                if wants(lin.weight):
                     _linear_wgrad(dy, x, lin.weight, rows)
-                if width is not None and _wants(lin.bias):
+                if width is not None and wants(lin.bias):
                     red_w.add(ops.colsum_partial(dy) if partial is None else partial,
                               grad_buffer(lin.bias), width)
                 grads_done(lin.weight)
@@ -1378,7 +1321,7 @@ class ViTBlockFn(torch.autograd.Function):
         # (thermal-only 0.13 ms faster per step; the fusion step 0.07 ms slower in round 3 and
         # 0.1 ms faster on the round-6 tree: _DGELU_COLSUM)
         cs1 = None
-        if (_DGELU_COLSUM == 2 or (_DGELU_COLSUM and ctx.beside)) and _wants(fc1_l.bias) and \
+        if (_DGELU_COLSUM == 2 or (_DGELU_COLSUM and ctx.beside)) and wants(fc1_l.bias) and \
                 g.is_cuda:
             cs1 = _empty((2 * ((rows + 255) // 256), Dh), F32, dev)
             try:
@@ -1391,19 +1334,19 @@ class ViTBlockFn(torch.autograd.Function):
         if cs1 is None:
             _linear_dgrad(rows, Dh, D, gb, fc2_l.weight, wfc2, dh_pre,
                           epilogue=L.EPI_BF16_DGELU, aux=dgl, ldaux=Dh)
-        if _wants(fc2_l.bias):
+        if wants(fc2_l.bias):
             _colsum_of_grad(gout if gout.dtype == F32 else g, grad_buffer(fc2_l.bias), red)
         wgrad(fc1_l, dh_pre, xn2, Dh, partial=cs1)
         dxn2 = _empty((rows, D), BF16, dev)
         _linear_dgrad(rows, D, Dh, dh_pre, fc1_l.weight, wfc1, dxn2, tile=ctx.t768)
         gmb = _empty((rows, D), BF16, dev)
         gsp = _ln_bwd(dxn2, xm, m2, r2, norm2, rows, D, g2, gmb,
-                      gsum=_wants(proj_l.bias), batch=red)  # g2 := g_mid (in place)
+                      gsum=wants(proj_l.bias), batch=red)  # g2 := g_mid (in place)
         # ---- attention branch: x_mid = x_in + proj(attn(norm1(x_in)))
         wgrad(proj_l, gmb, o)
         do = _empty((rows, D), BF16, dev)
         _linear_dgrad(rows, D, D, gmb, proj_l.weight, wproj, do, tile=ctx.t768)
-        if _wants(proj_l.bias):
+        if wants(proj_l.bias):
             red.add(gsp, grad_buffer(proj_l.bias), D)
         dqkv = ops.attention_bwd(qkv, o, do, lse, B, T, H, dh, attn.scale)
         wgrad(qkv_l, dqkv, xn1, 3 * D)
@@ -1445,7 +1388,7 @@ class TokenNormFn(torch.autograd.Function):
     def backward(ctx, g):
         if g.is_cuda:  # produced on the fusion head's stream; the ViT may run on a side stream
             arm_backward_join()
-            g.record_stream(ops.current_stream())
+            g.record_stream(current_stream())
         x, mean, rstd = ctx.saved_tensors
         norm = ctx.norm
         B, T, D = x.shape
@@ -1455,8 +1398,8 @@ class TokenNormFn(torch.autograd.Function):
         gxb = _empty((B, T, D), BF16, x.device)
         ops.zero_(gxb)
         gsp = ops.layernorm_bwd(g, D, False, x, T * D, mean, rstd, norm.weight, B, D, gx, T * D,
-                                gxb, grad_buffer(norm.weight) if _wants(norm.weight) else None,
-                                grad_buffer(norm.bias) if _wants(norm.bias) else None, gsum=True)
+                                gxb, grad_buffer(norm.weight) if wants(norm.weight) else None,
+                                grad_buffer(norm.bias) if wants(norm.bias) else None, gsum=True)
         grads_done(norm.weight, norm.bias)
         gx._dfu_bf16 = gxb
         gx._dfu_colsum = gsp  # only the class-token rows are non-zero: their sums are the total
@@ -1524,7 +1467,7 @@ class LinearFn(torch.autograd.Function):
                 if ctx.x_dtype != F32:
                     dx = dx.to(ctx.x_dtype)
                 dx = dx.view(*ctx.lead, K)
-            if _wants(w):
+            if wants(w):
                 # dW[n][k] += sum_r g[r][n] X[r][k]
                 ops.gemm_f32(N, K, rows, g, 1, N, xs, 1, K, grad_buffer(w), K, accumulate=True)
         else:
@@ -1542,10 +1485,10 @@ class LinearFn(torch.autograd.Function):
                 ops.gemm(rows, K, Np, gb, Np, wp, K, dx, K, b_mode=L.OPND_MNMAJOR,
                          epilogue=L.EPI_BF16 if out_bf else L.EPI_F32)
                 dx = dx.view(*ctx.lead, K)
-            if _wants(w):
+            if wants(w):
                 ops.gemm(N, K, rows, gb, gb.shape[1], xs, K, grad_buffer(w), K,
                          a_mode=L.OPND_MNMAJOR, b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
-        if _wants(b):
+        if wants(b):
             ops.colsum_add(g, grad_buffer(b))
         grads_done(w, b)
         return dx, None, None, None

@@ -8,8 +8,9 @@ on them fails as well (bench.py round 2: "event last recorded in a capturing str
 timing event went to torch.cuda.graph's capture stream, which its __exit__ leaves current when
 capture_end raises).
 try_capture ends such leftover captures (dfu_streams_abort_capture over every stream the step
-can touch), drops the per-stream caches that refer to them, and reports the failure, so the caller
-runs eager.
+can touch), drops the host state that refers to them (streams.forget), and reports the failure,
+so the caller runs eager.  The stream state itself -- which streams exist, which a capture has
+seen, what is cached per stream -- belongs to dfu_hip.streams; this module is capture logic only.
 """
 import ctypes
 import sys
@@ -18,32 +19,7 @@ import torch
 
 from . import _lib as L
 from . import functional as Fn
-from . import ops
-
-
-def _seen_streams():
-    """The streams library launches went to during the capture being recorded (ops.stream_ptr),
-    as torch streams -- user streams the step forked onto included."""
-    seen = ops._capture_seen
-    if not seen:
-        return []
-    return [torch.cuda.ExternalStream(raw, device=torch.device("cuda", dev))
-            for dev, raw in sorted(seen)]
-
-
-def step_streams(device=None, extra=()):
-    """Every stream a DFU step may enqueue on: the current one, the encoder side streams, the
-    ViT weight-gradient streams, the streams library launches went to during the capture in
-    progress, and `extra`."""
-    out = [torch.cuda.current_stream(device)]
-    out += list(Fn._side_streams.values()) + list(Fn._wgrad_streams.values()) + list(extra)
-    out += _seen_streams()
-    seen, uniq = set(), []
-    for s in out:
-        if s.cuda_stream not in seen:
-            seen.add(s.cuda_stream)
-            uniq.append(s)
-    return uniq
+from . import streams
 
 
 def capture_status(stream):
@@ -64,18 +40,18 @@ def join_forked(origin, extra=()):
     torch stream that the step did not join back (the C5 split-graph
     attempt's crash at hipStreamEndCapture) is joined here too; only non-library work on a
     stream the library never saw can still leave a fork unjoined."""
-    for s in step_streams(extra=extra):
+    for s in streams.known_streams(extra=extra):
         if s.cuda_stream != origin.cuda_stream and capture_status(s) == 1:
             origin.wait_stream(s)
 
 
-def abort_captures(streams):
-    """End any capture left active on `streams` (dfu_streams_abort_capture); returns
+def abort_captures(known):
+    """End any capture left active on the streams `known` (dfu_streams_abort_capture); returns
     (streams that were capturing, streams still capturing afterwards)."""
     lib = L.load()
-    handles = [s.cuda_stream for s in streams]
+    handles = [s.cuda_stream for s in known]
     before = 0
-    for s in streams:
+    for s in known:
         with torch.cuda.stream(s):
             before += int(torch.cuda.is_current_stream_capturing())
     arr = (ctypes.c_void_p * len(handles))(*handles)
@@ -88,21 +64,17 @@ def abort_captures(streams):
 def reset_after_failed_capture(extra=()):
     """Recover after a failed capture: end what HIP lets us end, retire the library-owned
     streams still capturing (HIP cannot end a capture whose origin's end already failed:
-    tools/diag/capture_unjoined.py) -- the next side_stream / wgrad_stream call makes fresh
-    ones -- and reset the host-side stream state.  Returns (streams that were capturing,
-    streams retired)."""
-    streams = step_streams(extra=extra)
-    n, _ = abort_captures(streams)
-    stuck = {s.cuda_stream for s in streams if capture_status(s) != 0}
-    for cache in (Fn._side_streams, Fn._wgrad_streams):
-        for k in [k for k, s in cache.items() if s.cuda_stream in stuck]:
-            del cache[k]  # leaked on purpose: a capturing stream cannot be destroyed or reused
+    tools/diag/capture_unjoined.py) -- the next side_stream / wgrad_stream / capture_stream call
+    makes fresh ones -- and reset the host-side stream state (streams.forget).  Returns (streams
+    that were capturing, streams retired)."""
+    known = streams.known_streams(extra=extra)
+    n, _ = abort_captures(known)
+    stuck = {s.cuda_stream for s in known if capture_status(s) != 0}
+    streams.forget(stuck)
     cur = torch.cuda.current_stream()
     if cur.cuda_stream in stuck:
         raise RuntimeError("dfu: the caller's stream is still capturing after a failed capture")
-    Fn._grad_streams.clear()
-    Fn._join_armed[0] = False
-    ops._stream_objs.clear()
+    Fn.disarm_backward_join()
     try:  # can the process run eager work again?  (an allocation + a kernel + a host sync)
         torch.empty(1024, device=cur.device).fill_(0.0)
         torch.cuda.synchronize()
@@ -116,51 +88,41 @@ def reset_after_failed_capture(extra=()):
     return n, len(stuck)
 
 
-_capture_streams = {}
-
-
 def try_capture(step, log=None, pool=None):
     """Capture `step()` into a torch.cuda.CUDAGraph on a fresh capture stream; returns the graph,
     or None after a failed capture (streams recovered, the failure reported through `log`,
     default stderr).  Work the step left on a forked stream is joined into the capture
     (join_forked).  The caller warms `step` up eagerly first, as graph capture requires."""
     prev = torch.cuda.current_stream()
-    # one library-owned capture stream per device, reused by every capture (a graph does not
-    # need its origin stream after the capture ends); retired, never reused, if a failure leaves
-    # it capturing
-    cap = _capture_streams.get(prev.device_index)
-    if cap is None:
-        cap = _capture_streams[prev.device_index] = Fn.new_stream(prev.device_index)
+    cap = streams.capture_stream(prev.device_index)
     cap.wait_stream(prev)
     # the capture stream's split-K tile counters exist before the capture: created inside it,
-    # their zero-fill would be recorded into this graph and run only at its replays
+    # their zero-fill would be recorded into this graph and run only at its replays (and once
+    # the recorder is on, creating a stream or a counter pool is refused)
     with torch.cuda.stream(cap):
-        ops.tile_counters(cap.device)
+        streams.tile_counters(cap.device)
     g = torch.cuda.CUDAGraph()
-    ops._capture_seen = set()
-    try:
-        with torch.cuda.graph(g, pool=pool, stream=cap):
-            try:
-                step()
-            finally:
-                # also when step() raised (a DfuError refusing a non-capturable call): joined
-                # forks let torch.cuda.graph's hipStreamEndCapture succeed, so the failure is a
-                # Python exception and the streams are clean for the eager fallback
-                join_forked(cap)
-        return g
-    except Exception as e:  # noqa: BLE001 -- any capture failure falls back to eager
-        # torch.cuda.graph.__exit__ leaves its capture stream current when capture_end raises
-        torch.cuda.set_stream(prev)
-        n, stuck = reset_after_failed_capture(extra=(cap,))
-        if capture_status(cap) != 0:
-            _capture_streams.pop(prev.device_index, None)  # leaked on purpose (see above)
-        msg = (f"[dfu] graph capture failed ({type(e).__name__}: {str(e).splitlines()[0]}); "
-               f"{n} stream(s) were left capturing, {stuck} retired; running eager")
-        if log is None:
-            print(msg, file=sys.stderr)
-        elif log:
-            log(msg)
-        del g
-        return None
-    finally:
-        ops._capture_seen = None
+    with streams.recording():  # through the recovery too, which aborts what the capture saw
+        try:
+            with torch.cuda.graph(g, pool=pool, stream=cap):
+                try:
+                    step()
+                finally:
+                    # also when step() raised (a DfuError refusing a non-capturable call):
+                    # joined forks let torch.cuda.graph's hipStreamEndCapture succeed, so the
+                    # failure is a Python exception and the streams are clean for the eager
+                    # fallback
+                    join_forked(cap)
+            return g
+        except Exception as e:  # noqa: BLE001 -- any capture failure falls back to eager
+            # torch.cuda.graph.__exit__ leaves its capture stream current when capture_end raises
+            torch.cuda.set_stream(prev)
+            n, stuck = reset_after_failed_capture(extra=(cap,))
+            msg = (f"[dfu] graph capture failed ({type(e).__name__}: {str(e).splitlines()[0]}); "
+                   f"{n} stream(s) were left capturing, {stuck} retired; running eager")
+            if log is None:
+                print(msg, file=sys.stderr)
+            elif log:
+                log(msg)
+            del g
+            return None

@@ -31,7 +31,7 @@ class Conv2d(tnn.Conv2d):
         R, S = self.kernel_size
         plain = R == 1 and S == 1 and self.stride == (1, 1) and self.padding == (0, 0)
         if C % 64 != 0 and not plain:
-            if Fn._krsc_strided(self.weight):
+            if Fn.krsc_strided(self.weight):
                 raise NotImplementedError(
                     "dfu_hip.nn.Conv2d: a channels-last (FusedAdamW) weight needs C % 64 == 0")
             return Conv2dIm2colFn.apply(x, self.weight, self)
@@ -68,7 +68,7 @@ class Conv2dIm2colFn(torch.autograd.Function):
         mod = ctx.mod
         Cout, M, K = wb.shape[0], B * P * Q, C * R * S
         dy = Fn.rows_view(Fn.nhwc_bf16(gy))
-        if Fn._wants(mod.weight):
+        if Fn.wants(mod.weight):
             ops.gemm(Cout, K, M, dy, Cout, col, Kp, Fn.grad_buffer(mod.weight).view(Cout, K), K,
                      a_mode=L.OPND_MNMAJOR, b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
             Fn.grads_done(mod.weight)
@@ -85,7 +85,7 @@ class Conv2dIm2colFn(torch.autograd.Function):
 
 class BatchNorm2d(tnn.BatchNorm2d):
     """torch.nn.BatchNorm2d.  Inside ResNet blocks the normalisation runs fused with the
-    producing convolution (statistics from its GEMM epilogue, functional._BN); standalone, the
+    producing convolution (statistics from its GEMM epilogue, functional.BNState); standalone, the
     tile statistics come from the stored input (dfu_bn_tile_stats) and the same finalize /
     apply / backward kernels run.  Output: bf16 channels_last."""
 
@@ -104,7 +104,7 @@ class BatchNorm2dFn(torch.autograd.Function):
                                       "128, 256 or a multiple of 512")
         M = B * H * W
         xr = Fn.rows_view(x)
-        st = Fn._BN(mod, M, C, x.device)
+        st = Fn.BNState(mod, M, C, x.device)
         st.forward_coeffs(ops.bn_tile_stats(xr, M, C) if st.training else None)
         out = torch.empty((M, C), dtype=torch.bfloat16, device=x.device)
         ops.bn_apply(xr, st.scale, st.shift, None, 0, out, M, C)
@@ -196,8 +196,8 @@ class LayerNormFn(torch.autograd.Function):
         ops.zero_(gx)
         ops.layernorm_bwd(g.reshape(rows, D).float().contiguous(), D, False, x2, D, mean, rstd,
                           mod.weight, rows, D, gx, D, None,
-                          Fn.grad_buffer(mod.weight) if Fn._wants(mod.weight) else None,
-                          Fn.grad_buffer(mod.bias) if Fn._wants(mod.bias) else None)
+                          Fn.grad_buffer(mod.weight) if Fn.wants(mod.weight) else None,
+                          Fn.grad_buffer(mod.bias) if Fn.wants(mod.bias) else None)
         Fn.grads_done(mod.weight, mod.bias)
         return gx.view(ctx.shape), None, None, None
 

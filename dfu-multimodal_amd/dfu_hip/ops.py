@@ -10,6 +10,9 @@ import torch
 
 from . import _lib as L
 from ._lib import check
+# the stream helpers of the launch path (dfu_hip.streams), also known by ops.<name>
+from .streams import (TILE_COUNTERS, current_stream, on_stream, refuse_in_capture,  # noqa: F401
+                      stream_ptr, stream_wait, tile_counters)
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -18,112 +21,6 @@ F16 = torch.float16
 
 def lib():
     return L.load()
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-_cur_device = getattr(torch._C, "_cuda_getDevice", None)
-
-
-# (device, raw stream) of every launch while dfu_hip.graphs.try_capture records a graph (None
-# otherwise): the capture joins each of these streams that is still capturing into its origin
-# before hipStreamEndCapture, so library work a step left on a stream it forked -- a plain torch
-# stream included -- becomes part of the graph instead of failing the capture as unjoined.
-_capture_seen = None
-
-
-def stream_ptr():
-    """The current HIP stream of the current device (the raw-pointer query: torch.cuda.
-    current_stream() builds a Stream object per call, ~8 us of host time x ~260 calls a step).
-    Pointers go to the C ABI as plain ints (ctypes converts them for c_void_p parameters:
-    0.4 us per argument less than a c_void_p object, ~2000 arguments a step)."""
-    if _raw_stream is not None and _cur_device is not None:
-        dev = _cur_device()
-        s = _raw_stream(dev)
-    else:
-        st = torch.cuda.current_stream()
-        dev, s = st.device_index, st.cuda_stream
-    if _capture_seen is not None:
-        _capture_seen.add((dev, s))
-    return s
-
-
-_get_cur_stream = getattr(torch._C, "_cuda_getCurrentStream", None)
-_set_cur_stream = getattr(torch._C, "_cuda_setStream", None)
-_stream_objs = {}
-
-
-def current_stream(idx=None):
-    """torch.cuda.current_stream(idx) as one cached Stream object per (device, raw HIP stream):
-    torch builds a new object per call (2.7 us of host time against 0.2 us,
-    tools/host_breakdown.py).  A cached object is re-validated against the raw handle, so a
-    destroyed user stream whose address is reused gets a fresh object."""
-    if _raw_stream is None or _cur_device is None:
-        return torch.cuda.current_stream(idx)
-    if idx is None:
-        idx = _cur_device()
-    raw = _raw_stream(idx)
-    st = _stream_objs.get((idx, raw))
-    if st is None or st.cuda_stream != raw:
-        st = _stream_objs[(idx, raw)] = torch.cuda.current_stream(idx)
-    return st
-
-
-class on_stream:
-    """``with torch.cuda.stream(s):`` for a stream of the current device without the Stream
-    object torch's context builds on entry (5.9 us of host time per entry against ~1 us,
-    tools/host_breakdown.py); any other case goes through torch's own context."""
-
-    __slots__ = ("s", "prev")
-
-    def __init__(self, s):
-        self.s = s
-        self.prev = None
-
-    def __enter__(self):
-        s = self.s
-        if s is None:
-            return None
-        if _get_cur_stream is None or _set_cur_stream is None or _cur_device is None or \
-                s.device_index != _cur_device():
-            self.prev = torch.cuda.stream(s)
-            self.prev.__enter__()
-            return s
-        dev = s.device_index
-        self.prev = _get_cur_stream(dev)
-        _set_cur_stream(s.stream_id, dev, s.device_type)
-        return s
-
-    def __exit__(self, *exc):
-        p, self.prev = self.prev, None
-        if isinstance(p, tuple):
-            _set_cur_stream(p[0], p[1], p[2])
-        elif p is not None:
-            p.__exit__(*exc)
-        return False
-
-
-def stream_wait(waiter, producer):
-    """waiter.wait_stream(producer) for torch streams of the current device by one C call
-    (dfu_stream_wait: a pooled event instead of a torch Event object per call, 6.5 us of host
-    time against ~2 us); any other case goes through torch."""
-    dev = waiter.device_index
-    if producer.device_index != dev or _cur_device is None or dev != _cur_device():
-        waiter.wait_stream(producer)
-        return
-    w = waiter.cuda_stream
-    if _capture_seen is not None:  # a fork into a capture: try_capture joins it at the end
-        _capture_seen.add((dev, w))
-    check(lib().dfu_stream_wait(w, producer.cuda_stream), "dfu_stream_wait")
-
-
-def refuse_in_capture(what):
-    """Raise DfuError when the current stream is recording a graph: `what` would either
-    invalidate the capture (a stream creation is not a capturable call) or leave state that
-    only a replay initialises (a zero-fill recorded into the graph)."""
-    if torch.cuda.is_current_stream_capturing():
-        stream_ptr()  # a fork with no library launch yet: join_forked must still see it
-        raise L.DfuError(f"{what} requested inside a HIP-graph capture: run the step once "
-                         f"eagerly on the same streams before capturing it")
 
 
 def ptr(t):
@@ -253,41 +150,6 @@ def gemm(M, N, K, A, lda, B, ldb, C, ldc, a_mode=L.OPND_KMAJOR, b_mode=L.OPND_KM
         executed = 3.0 * flops if x3 else 2.0 * M * N * K
         gemm_record.append((d, flops, _algorithmic_bytes(d, conv),
                             (A, B, C, bias, aux, aux_out, stats, workspace, a_lo), executed))
-
-
-_COUNTERS = {}
-_COUNTER_POOLS = {}  # device index -> [zeroed pool, next free slot]
-TILE_COUNTERS = 1 << 16
-COUNTER_SLOTS = 64  # streams per pool (64 x 256 KiB)
-
-
-def tile_counters(device):
-    """Per-stream zeroed int32 tile counters for the in-kernel split-K reduction (every launch
-    returns them zeroed; launches on one stream never overlap).  A stream's counters are a slot
-    of a per-device pool zeroed when the pool is made, so a stream first seen inside a graph
-    capture takes a slot by host bookkeeping alone (a zero-fill made inside the capture would be
-    recorded into the graph and run only at its replays: eager launches on that stream before
-    the first replay would read uninitialised counters)."""
-    idx = device.index if isinstance(device, torch.device) and device.index is not None else None
-    if _raw_stream is not None and idx is not None:
-        key = (idx, _raw_stream(idx))  # the raw query: ~0.3 us against ~5 us for a Stream object
-        t = _COUNTERS.get(key)
-        if t is not None:
-            return t
-    st = torch.cuda.current_stream(device)
-    key = (st.device_index, st.cuda_stream)
-    t = _COUNTERS.get(key)
-    if t is None:
-        pool = _COUNTER_POOLS.get(st.device_index)
-        if pool is None or pool[1] == COUNTER_SLOTS:
-            refuse_in_capture(f"a fresh pool of split-K tile counters (stream "
-                              f"{st.cuda_stream:#x})")
-            pool = _COUNTER_POOLS[st.device_index] = [
-                torch.zeros(COUNTER_SLOTS * TILE_COUNTERS, dtype=torch.int32, device=device), 0]
-        i = pool[1]
-        pool[1] += 1
-        t = _COUNTERS[key] = pool[0][i * TILE_COUNTERS:(i + 1) * TILE_COUNTERS]
-    return t
 
 
 def gemm_set_tail_split(enable):

@@ -32,6 +32,7 @@ import torch.distributed as dist
 
 from . import functional as Fn
 from . import ops
+from . import streams
 
 # elements: every tensor view starts 128-byte aligned, and a parameter's 32-element blocks are
 # the flat buffer's (the interleaved-pair x3 shadow's blocks, enable_x3)
@@ -372,11 +373,11 @@ class FusedAdamW(torch.optim.Optimizer):
         touched = fp.grad._version != self._grad_version
         if (self.early_update and fp.data.is_cuda and not _dp_world() and not rebind
                 and not touched):
-            early = self._early_range(ops.current_stream(fp.data.get_device()))
-        cur = ops.current_stream(fp.data.get_device()) if fp.data.is_cuda else None
+            early = self._early_range(streams.current_stream(fp.data.get_device()))
+        cur = streams.current_stream(fp.data.get_device()) if fp.data.is_cuda else None
         if early is not None:
             lo, hi, st = early
-            with ops.on_stream(st):
+            with streams.on_stream(st):
                 ops.step_increment(self.step_dev)  # the rest runs after the join: sees it
                 self._adamw(lo, hi)
                 # the block's transposed shadows right behind its update, beside the other
@@ -384,8 +385,9 @@ class FusedAdamW(torch.optim.Optimizer):
                 inside = fp.range_jobs(lo, hi)[0] if fp.t_jobs is not None and _EARLY_T else None
                 if inside is not None:
                     inside.launch()
-            ops.stream_wait(cur, st)  # the rest, the step counter and the shadow transposes after it
-        Fn.join_grad_streams()
+            # the rest, the step counter and the shadow transposes after it
+            streams.stream_wait(cur, st)
+        streams.join_grad_streams()
         if rebind:
             fp.rebind_grads()
         if early is None:

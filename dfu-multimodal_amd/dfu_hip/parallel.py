@@ -15,7 +15,7 @@ import torch
 import torch.distributed as dist
 
 from . import functional as Fn
-from . import ops
+from . import streams
 
 
 def init_from_env(backend=None):
@@ -176,13 +176,13 @@ class GradAllReducer:
         if self.cuda:
             carrier = self._carrier(k, carrier)
             if carrier is None:
-                carrier = ops.current_stream()
-                Fn.join_grad_streams(carrier, clear=False)
+                carrier = streams.current_stream()
+                streams.join_grad_streams(carrier, clear=False)
             for sid, (st, ev) in self._marks[k].items():
                 if st is not carrier:
                     carrier.wait_event(ev)
             self.carriers[carrier.cuda_stream] = carrier
-            with ops.on_stream(carrier):
+            with streams.on_stream(carrier):
                 self._works.append(self._reduce(view))
         else:
             self._works.append(self._reduce(view))
@@ -210,7 +210,7 @@ class GradAllReducer:
             self._launch(k, st)
 
     def finish(self):
-        Fn.join_grad_streams()
+        streams.join_grad_streams()
         if self.world <= 1:
             return
         if self._issued is None:

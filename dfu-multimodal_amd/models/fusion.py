@@ -11,7 +11,7 @@ import torch.nn as tnn
 
 from dfu_hip import functional as Fn
 from dfu_hip import nn as hnn
-from dfu_hip import ops
+from dfu_hip import streams
 
 from .encoders import resnet50, vit_base_patch16_224
 
@@ -69,7 +69,7 @@ def _interleave(rgen, vgen, side):
             if i == 0:
                 next(rgen)
             else:
-                with ops.on_stream(side):
+                with streams.on_stream(side):
                     next(vgen)
         except StopIteration as e:
             out[i] = e.value
@@ -124,22 +124,22 @@ class MultimodalFusionModel(tnn.Module):
         """Both encoders; on the GPU the thermal ViT runs on a side stream concurrently with the
         ResNet on the current stream (their kernels fill each other's idle CUs).  Backward ops
         run on their forward op's stream (autograd), and parameter-gradient producers are
-        joined by FusedAdamW.step / GradAllReducer.finish (functional.join_grad_streams)."""
+        joined by FusedAdamW.step / GradAllReducer.finish (streams.join_grad_streams)."""
         if not (self.concurrent_branches and rgb.is_cuda):
             return rgb_net(rgb), th_net(thermal)
-        main = ops.current_stream()
-        side = Fn.side_stream(rgb.device)
-        ops.stream_wait(side, main)
+        main = streams.current_stream()
+        side = streams.side_stream(rgb.device)
+        streams.stream_wait(side, main)
         with Fn.concurrent_encoders():
             thermal.record_stream(side)
             if _INTERLEAVE and _stageable(rgb_net) and _stageable(th_net):
                 rgb_feat, th_feat = _interleave(rgb_net.forward_stages(rgb),
                                                 th_net.forward_stages(thermal), side)
             else:
-                with ops.on_stream(side):
+                with streams.on_stream(side):
                     th_feat = th_net(thermal)
                 rgb_feat = rgb_net(rgb)
-        ops.stream_wait(main, side)
+        streams.stream_wait(main, side)
         th_feat.record_stream(main)
         return rgb_feat, th_feat
 

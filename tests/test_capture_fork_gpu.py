@@ -6,14 +6,15 @@ ways such a fork breaks a capture, each handled now:
   * library work left on the fork, not joined back: dfu_hip.graphs.join_forked only knew the
     library's own streams, so the origin's hipStreamEndCapture failed as unjoined -- which HIP
     cannot undo.  try_capture now records every stream a library launch goes to while it
-    captures (ops.stream_ptr) and joins each one still capturing;
+    captures (streams.stream_ptr) and joins each one still capturing;
   * per-stream state first created inside the capture: the split-K tile counters of a stream
     never used before (their zero-fill was recorded into the graph, so eager launches on that
     stream before the first replay read uninitialised counters) -- now a slot of a per-device
     pool zeroed beforehand, taken by host bookkeeping; and a new library stream
     (hipStreamCreate is not capturable: it invalidates the capture of every fork) -- now
-    refused with DfuError before the call: the capture joins its forks, ends cleanly, and
-    try_capture returns None (eager fallback);
+    refused with DfuError before the call, whether or not the requesting stream is itself
+    capturing: the capture joins its forks, ends cleanly, and try_capture returns None (eager
+    fallback);
   * non-library work on a fork the step leaves unjoined: the library cannot see it; the capture
     fails and try_capture recovers (or raises a RuntimeError naming the condition).
 Each case runs in a child process, so a crash fails this test instead of the test session."""
@@ -137,6 +138,26 @@ CHILD = textwrap.dedent(r'''
     res["stream_created_in_capture"] = dict(captured=g is not None, log=msgs,
                                             eager_equal=bool(torch.equal(C2, ref2)))
 
+    # 6. a library stream requested inside the capture from a current stream that is not itself
+    #    capturing (made current without a fork into it): hipStreamCreate there would still
+    #    invalidate the global-mode capture, so it is refused like case 4
+    aside = torch.cuda.Stream()
+    with torch.cuda.stream(aside):
+        scratch.add_(1.0)  # used once before the capture
+    torch.cuda.current_stream().wait_stream(aside)
+    torch.cuda.synchronize()
+
+    def step6():
+        with torch.cuda.stream(aside):
+            Fn.new_stream(torch.cuda.current_device())
+    msgs = []
+    g = graphs.try_capture(step6, log=msgs.append)
+    C2.zero_()
+    wgrad(C2)
+    torch.cuda.synchronize()
+    res["stream_requested_beside_capture"] = dict(captured=g is not None, log=msgs,
+                                                  eager_equal=bool(torch.equal(C2, ref2)))
+
     # 3. non-library work on a fork the step leaves unjoined
     other = torch.cuda.Stream()
     x = torch.zeros(1 << 20, device=DEV)
@@ -186,6 +207,9 @@ def test_capture_fork_onto_plain_torch_stream():
     r4 = res["stream_created_in_capture"]
     assert not r4["captured"] and r4["eager_equal"], r4
     assert any("DfuError" in m and "inside a HIP-graph capture" in m for m in r4["log"]), r4
+    r6 = res["stream_requested_beside_capture"]
+    assert not r6["captured"] and r6["eager_equal"], r6
+    assert any("DfuError" in m and "inside a HIP-graph capture" in m for m in r6["log"]), r6
     r3 = res["unjoined_torch_fork"]
     # the library cannot join work it never saw: a Python-level failure, never a crash
     assert not r3["captured"], r3

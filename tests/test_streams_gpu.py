@@ -1,6 +1,8 @@
-"""The host-side stream helpers of the hot path (dfu_hip.ops): dfu_stream_wait (a pooled event
-per join instead of a torch Event object), the cached current-stream objects and the stream
-context without a Stream object per entry -- each against torch's own behaviour."""
+"""The host-side stream helpers of the hot path (dfu_hip.streams, also known by ops.<name>):
+dfu_stream_wait (a pooled event per join instead of a torch Event object), the cached
+current-stream objects and the stream context without a Stream object per entry -- each against
+torch's own behaviour -- and the stream state that module owns: the library's streams by role,
+the per-stream caches and their reset (streams.forget)."""
 import pytest
 import torch
 
@@ -72,3 +74,46 @@ def test_current_stream_is_cached_and_follows_the_context():
         b = ops.current_stream()
         assert b == s and b.cuda_stream == s.cuda_stream
     assert ops.current_stream() is a
+
+
+def test_library_streams_are_one_per_role():
+    from dfu_hip import streams
+    dev = torch.device("cuda", 0)
+    side, wgrad = streams.side_stream(dev), streams.wgrad_stream(dev)
+    cap = streams.capture_stream(0)
+    assert streams.side_stream(dev) is side
+    assert streams.wgrad_stream(dev) is wgrad
+    assert streams.capture_stream(0) is cap
+    assert len({side.cuda_stream, wgrad.cuda_stream, cap.cuda_stream}) == 3
+
+
+def test_forget_evicts_a_retired_stream_from_every_cache():
+    from dfu_hip import streams
+    dev = torch.device("cuda", 0)
+    side = streams.side_stream(dev)
+    old = side.cuda_stream
+    with streams.on_stream(side):
+        streams.tile_counters(dev)
+        assert streams.current_stream().cuda_stream == old
+    objs, counters = streams.cached_handles()
+    assert old in objs and old in counters
+    assert old in [s.cuda_stream for s in streams.known_streams()]
+    streams.forget({old})
+    objs, counters = streams.cached_handles()
+    assert old not in objs and old not in counters
+    assert old not in [s.cuda_stream for s in streams.known_streams()]
+    fresh = streams.side_stream(dev)
+    assert fresh.cuda_stream != old  # the retired stream is leaked, so its address is not reused
+    with streams.on_stream(fresh):
+        cnt = streams.tile_counters(dev)
+    torch.cuda.synchronize()
+    assert cnt.numel() == streams.TILE_COUNTERS and int(cnt.abs().sum().item()) == 0
+
+
+def test_known_streams_lists_a_stream_once():
+    from dfu_hip import streams
+    s = torch.cuda.Stream()
+    handles = [k.cuda_stream for k in streams.known_streams(extra=[s, s])]
+    assert handles.count(s.cuda_stream) == 1
+    assert len(handles) == len(set(handles))
+    assert handles[0] == torch.cuda.current_stream().cuda_stream
