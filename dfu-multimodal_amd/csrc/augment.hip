@@ -16,6 +16,9 @@
 //   per image reduces it first (k_augment_stats).
 // Random parameters are drawn on the host (data/gpu_transforms.py) and arrive per image as
 // dfu_aug_params; all arithmetic here is integer except the blends and the normalisation.
+// Test-time augmentation (notebooks/test_time_augmentation.py:145-167) uses the same two kernels
+// through dfu_augment_views: K outputs gathered from one resized image (view_src), and the TTA
+// Compose's order, rotation before the flips.
 #include <cmath>
 #include <vector>
 
@@ -101,12 +104,22 @@ DFU_DEV bool affine_src(const int32_t* a, int x, int y, int W, int H, int& xs, i
   return xs >= 0 && xs < W && ys >= 0 && ys < H;
 }
 
-// The flipped + rotated resized image at (x, y); rotation fill is black.
+// The resized image after its flips and rotation, at (x, y); rotation fill is black.  ORDER is
+// the Compose's: DFU_AUG_ORDER_FLIP_ROTATE flips first (the train scripts), so the inverse chain
+// is rotation map -> un-flip -> fetch; DFU_AUG_ORDER_ROTATE_FLIP rotates first (the TTA script),
+// so it is un-flip -> rotation map -> fetch.
+template <int ORDER>
 DFU_DEV Px rotated(const uint8_t* im, const dfu_aug_params& P, int W, int H, int x, int y) {
   Px p = {{0, 0, 0}};
+  if (ORDER == DFU_AUG_ORDER_ROTATE_FLIP) {
+    if (P.hflip) x = W - 1 - x;
+    if (P.vflip) y = H - 1 - y;
+  }
   if (P.rotate && !affine_src(P.rot, x, y, W, H, x, y)) return p;
-  if (P.hflip) x = W - 1 - x;
-  if (P.vflip) y = H - 1 - y;
+  if (ORDER == DFU_AUG_ORDER_FLIP_ROTATE) {
+    if (P.hflip) x = W - 1 - x;
+    if (P.vflip) y = H - 1 - y;
+  }
   const uint8_t* q = im + ((int64_t)y * W + x) * 3;
   p.c[0] = q[0];
   p.c[1] = q[1];
@@ -157,28 +170,42 @@ DFU_DEV int contrast_slot(const dfu_aug_params& P) {
 // order does not matter).  sum <= 255 * H * W fits int32 for H * W < 8.4M.
 constexpr int kStatBlocks = 8;
 
+// Output image v reads resized image view_src[v] (v itself without view_src); -1 for an index
+// outside [0, n_images), whose output is the fill.
+DFU_DEV int view_image(const int32_t* view_src, int v, int n_images) {
+  const int s = view_src ? view_src[v] : v;
+  return s >= 0 && s < n_images ? s : -1;
+}
+
+template <int ORDER>
 __global__ void __launch_bounds__(256) k_augment_stats(const uint8_t* __restrict__ img,
                                                        const dfu_aug_params* __restrict__ params,
-                                                       int H, int W, int32_t* __restrict__ sums) {
+                                                       const int32_t* __restrict__ view_src,
+                                                       int n_images, int H, int W,
+                                                       int32_t* __restrict__ sums) {
   const dfu_aug_params P = params[blockIdx.y];
   const int slot = contrast_slot(P);
-  if (slot < 0) return;
-  const uint8_t* im = img + (int64_t)blockIdx.y * H * W * 3;
+  const int src = view_image(view_src, blockIdx.y, n_images);
+  if (slot < 0 || src < 0) return;
+  const uint8_t* im = img + (int64_t)src * H * W * 3;
   int s = 0;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < H * W; i += gridDim.x * blockDim.x) {
-    const Px p = colour(rotated(im, P, W, H, i % W, i / W), P, slot, 0);
+    const Px p = colour(rotated<ORDER>(im, P, W, H, i % W, i / W), P, slot, 0);
     s += grey(p);
   }
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   if ((threadIdx.x & 63) == 0) atomicAdd(sums + blockIdx.y, s);
 }
 
+template <int ORDER>
 __global__ void k_augment_apply(const uint8_t* __restrict__ img,
                                 const dfu_aug_params* __restrict__ params,
+                                const int32_t* __restrict__ view_src, int n_images,
                                 const int32_t* __restrict__ means, int H, int W, float m0, float m1,
                                 float m2, float s0, float s1, float s2, float* __restrict__ out) {
   const dfu_aug_params P = params[blockIdx.y];
-  const uint8_t* im = img + (int64_t)blockIdx.y * H * W * 3;
+  const int src = view_image(view_src, blockIdx.y, n_images);
+  const uint8_t* im = img + (int64_t)(src < 0 ? 0 : src) * H * W * 3;
   const int n = H * W;
   // == int(sum / n + 0.5), ImageStat's mean rounded as ImageEnhance.Contrast does
   const int mean = contrast_slot(P) >= 0 ? (int)((2 * (int64_t)means[blockIdx.y] + n) / (2 * (int64_t)n)) : 0;
@@ -186,12 +213,31 @@ __global__ void k_augment_apply(const uint8_t* __restrict__ img,
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     int x = i % W, y = i / W;
     Px p = {{0, 0, 0}};
-    if (!P.affine || affine_src(P.aff, x, y, W, H, x, y))
-      p = colour(rotated(im, P, W, H, x, y), P, P.n_ops, mean);
+    if (src >= 0 && (!P.affine || affine_src(P.aff, x, y, W, H, x, y)))
+      p = colour(rotated<ORDER>(im, P, W, H, x, y), P, P.n_ops, mean);
     o[i] = ((float)p.c[0] / 255.f - m0) / s0;
     o[n + i] = ((float)p.c[1] / 255.f - m1) / s1;
     o[2 * n + i] = ((float)p.c[2] / 255.f - m2) / s2;
   }
+}
+
+// The two launches behind dfu_augment_normalize (view_src NULL: image v -> output v) and
+// dfu_augment_views.
+template <int ORDER>
+int launch_augment(const uint8_t* img, const dfu_aug_params* params, const int32_t* view_src,
+                   int n_images, int n_out, int H, int W, const float* mean3, const float* std3,
+                   int32_t* contrast_means, float* out, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(contrast_means, 0, sizeof(int32_t) * n_out, stream);
+  DFU_CHECK_ARG(e == hipSuccess, "augment: memset: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(k_augment_stats<ORDER>, dim3(kStatBlocks, n_out), dim3(256), 0, stream, img,
+                     params, view_src, n_images, H, W, contrast_means);
+  DFU_LAUNCH_CHECK();
+  const int gx = (H * W + TPB - 1) / TPB;
+  hipLaunchKernelGGL(k_augment_apply<ORDER>, dim3(gx < 64 ? gx : 64, n_out), dim3(TPB), 0, stream,
+                     img, params, view_src, n_images, contrast_means, H, W, mean3[0], mean3[1],
+                     mean3[2], std3[0], std3[1], std3[2], out);
+  DFU_LAUNCH_CHECK();
+  return DFU_OK;
 }
 
 }  // namespace
@@ -260,15 +306,26 @@ extern "C" int dfu_augment_normalize(const uint8_t* img, const dfu_aug_params* p
   DFU_CHECK_ARG(img && params && mean3 && std3 && contrast_means && out && n > 0 && H > 0 &&
                     W > 0 && (int64_t)H * W * 255 < (1ll << 31),
                 "dfu_augment_normalize: bad args");
-  hipError_t e = hipMemsetAsync(contrast_means, 0, sizeof(int32_t) * n, (hipStream_t)stream);
-  DFU_CHECK_ARG(e == hipSuccess, "dfu_augment_normalize: memset: %s", hipGetErrorString(e));
-  hipLaunchKernelGGL(k_augment_stats, dim3(kStatBlocks, n), dim3(256), 0, (hipStream_t)stream,
-                     img, params, H, W, contrast_means);
-  DFU_LAUNCH_CHECK();
-  const int gx = (H * W + TPB - 1) / TPB;
-  hipLaunchKernelGGL(k_augment_apply, dim3(gx < 64 ? gx : 64, n), dim3(TPB), 0,
-                     (hipStream_t)stream, img, params, contrast_means, H, W, mean3[0], mean3[1],
-                     mean3[2], std3[0], std3[1], std3[2], out);
-  DFU_LAUNCH_CHECK();
-  return DFU_OK;
+  return launch_augment<DFU_AUG_ORDER_FLIP_ROTATE>(img, params, nullptr, n, n, H, W, mean3, std3,
+                                                   contrast_means, out, (hipStream_t)stream);
+}
+
+extern "C" int dfu_augment_views(const uint8_t* img, int32_t n_images,
+                                 const dfu_aug_params* params, const int32_t* view_src,
+                                 int32_t n_views, int32_t order, int32_t H, int32_t W,
+                                 const float* mean3, const float* std3, int32_t* contrast_means,
+                                 float* out, void* stream) {
+  DFU_CHECK_ARG(img && params && view_src && mean3 && std3 && contrast_means && out &&
+                    n_images > 0 && n_views > 0 && n_views <= 65535 && H > 0 && W > 0 &&
+                    (int64_t)H * W * 255 < (1ll << 31),
+                "dfu_augment_views: bad args");
+  DFU_CHECK_ARG(order == DFU_AUG_ORDER_FLIP_ROTATE || order == DFU_AUG_ORDER_ROTATE_FLIP,
+                "dfu_augment_views: order %d", order);
+  if (order == DFU_AUG_ORDER_ROTATE_FLIP)
+    return launch_augment<DFU_AUG_ORDER_ROTATE_FLIP>(img, params, view_src, n_images, n_views, H,
+                                                     W, mean3, std3, contrast_means, out,
+                                                     (hipStream_t)stream);
+  return launch_augment<DFU_AUG_ORDER_FLIP_ROTATE>(img, params, view_src, n_images, n_views, H, W,
+                                                   mean3, std3, contrast_means, out,
+                                                   (hipStream_t)stream);
 }

@@ -16,6 +16,11 @@ skips; ColorJitter `randperm(4)` then brightness, contrast, saturation factors
 `uniform_(1 - 0.3, 1 + 0.3)`; RandomAffine angle, tx, ty (`int(round(uniform_(-0.1 W, 0.1 W)))`),
 scale.  The pixel arithmetic given those parameters is pinned against PIL itself
 (tests/test_augment_gpu.py); the draw order is "parity unpinned" (torchvision absent).
+
+Test-time augmentation (notebooks/test_time_augmentation.py:145-167): `rgb_tta_transform` /
+`thermal_tta_transform` put the rotation before the flips (TransformSpec.order) and use a bare
+RandomAffine without a scale; `views=K` on the preprocessor and the loaders gives K views per
+image from one decode, one copy and one resize (dfu_augment_views; tests/test_tta_gpu.py).
 """
 import ctypes
 import math
@@ -54,10 +59,13 @@ class TransformSpec:
     rotation: float = 0.0                     # RandomRotation(degrees); 0 = absent
     jitter: tuple = None                      # ColorJitter(brightness, contrast, saturation)
     jitter_p: float = 0.0
-    affine: tuple = None                      # RandomAffine(degrees, translate, scale)
-    affine_p: float = 0.0
+    affine: tuple = None                      # RandomAffine(degrees, translate, scale);
+                                              # scale None = no scale argument (no draw, 1.0)
+    affine_p: float = 0.0                     # RandomApply's p; None = a bare RandomAffine
     mean: tuple = IMAGENET_MEAN
     std: tuple = IMAGENET_STD
+    order: str = "flip_rotate"                # flips then rotation (the train scripts), or
+                                              # "rotate_flip" (test_time_augmentation.py)
 
     @property
     def random(self):
@@ -73,6 +81,15 @@ thermal_train_transform = TransformSpec(hflip_p=0.5, vflip_p=0.5, rotation=30,
                                         affine=(20, (0.1, 0.1), (0.8, 1.2)), affine_p=AUG_PROB,
                                         mean=THERMAL_MEAN, std=THERMAL_STD)
 thermal_val_test_transform = TransformSpec(mean=THERMAL_MEAN, std=THERMAL_STD)
+# test_time_augmentation.py:145-167 get_light_augmentation_transforms: Resize, RandomRotation(15),
+# the two flips, a bare RandomAffine(10, translate=(0.05, 0.05)), ToTensor, Normalize
+rgb_tta_transform = TransformSpec(hflip_p=0.5, vflip_p=0.5, rotation=15,
+                                  affine=(10, (0.05, 0.05), None), affine_p=None,
+                                  order="rotate_flip")
+thermal_tta_transform = TransformSpec(hflip_p=0.5, vflip_p=0.5, rotation=15,
+                                      affine=(10, (0.05, 0.05), None), affine_p=None,
+                                      mean=THERMAL_MEAN, std=THERMAL_STD, order="rotate_flip")
+ORDERS = {"flip_rotate": 0, "rotate_flip": 1}  # enum dfu_aug_order
 
 
 @dataclass
@@ -91,27 +108,33 @@ def _uniform(a, b, g):
 
 def sample_params(spec, generator=None):
     """Draw one sample's parameters in the order torchvision's Compose consumes the torch RNG
-    (generator None = the global RNG, as the reference's transforms use)."""
+    (generator None = the global RNG, as the reference's transforms use).  spec.order places
+    the rotation angle after the flip coins ("flip_rotate") or before them ("rotate_flip")."""
     g = generator
     p = AugParams()
     H, W = spec.size
+    if spec.order not in ORDERS:
+        raise ValueError(f"TransformSpec.order {spec.order!r}")
+    if spec.rotation and spec.order == "rotate_flip":
+        p.angle = _uniform(-float(spec.rotation), float(spec.rotation), g)
     if spec.hflip_p:
         p.hflip = bool(torch.rand(1, generator=g) < spec.hflip_p)
     if spec.vflip_p:
         p.vflip = bool(torch.rand(1, generator=g) < spec.vflip_p)
-    if spec.rotation:
+    if spec.rotation and spec.order == "flip_rotate":
         p.angle = _uniform(-float(spec.rotation), float(spec.rotation), g)
     if spec.jitter is not None and not (spec.jitter_p < torch.rand(1, generator=g)):
         order = torch.randperm(4, generator=g).tolist()
         f = [_uniform(max(0.0, 1 - v), 1 + v, g) for v in spec.jitter]
         p.ops = [(k, f[k]) for k in order if k < 3]   # hue (3) is None in the reference
-    if spec.affine is not None and not (spec.affine_p < torch.rand(1, generator=g)):
-        deg, (tr_x, tr_y), (s0, s1) = spec.affine
+    if spec.affine is not None and (spec.affine_p is None
+                                    or not (spec.affine_p < torch.rand(1, generator=g))):
+        deg, (tr_x, tr_y), scale_range = spec.affine
         angle = _uniform(-float(deg), float(deg), g)
         max_dx, max_dy = float(tr_x * W), float(tr_y * H)
         tx = int(round(_uniform(-max_dx, max_dx, g)))
         ty = int(round(_uniform(-max_dy, max_dy, g)))
-        scale = _uniform(s0, s1, g)
+        scale = _uniform(*scale_range, g) if scale_range is not None else 1.0
         p.affine = (angle, (tx, ty), scale, (0.0, 0.0))
     return p
 
@@ -219,21 +242,29 @@ class GpuPreprocessor:
         self._mean = (ctypes.c_float * 3)(*spec.mean)
         self._std = (ctypes.c_float * 3)(*spec.std)
 
-    def __call__(self, images, params=None):
-        return self.run(self.stage(images, params))
+    def __call__(self, images, params=None, views=None):
+        return self.run(self.stage(images, params, views))
 
-    def stage(self, images, params=None):
+    def stage(self, images, params=None, views=None):
         """Host side of one batch: pack descriptors, parameters, resize taps and pixels into one
-        pinned buffer and start its single H2D copy on the current stream."""
+        pinned buffer and start its single H2D copy on the current stream.  views=K (test-time
+        augmentation): K parameter records per image, sample-major (view v of image i at
+        i * K + v); the images are still staged, copied and resized once."""
         spec = self.spec
         OH, OW = spec.size
         n = len(images)
+        if views is None and spec.order != "flip_rotate":
+            views = 1  # dfu_augment_normalize has the train scripts' order only
+        if views is not None and views < 1:
+            raise ValueError(f"views = {views}")
         if n == 0:
-            return _Staged(None, 0, 0, 0, 0, 0)
+            return _Staged(None, 0, 0, 0, 0, 0, views)
+        nv = n * (views or 1)
         if params is None:
-            params = [AugParams() for _ in range(n)]
-        if len(params) != n:
-            raise ValueError("one AugParams per image")
+            params = [AugParams() for _ in range(nv)]
+        if len(params) != nv:
+            raise ValueError("one AugParams per image" if views is None
+                             else f"{views} AugParams per image, sample-major")
         imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
         for im in imgs:
             if im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
@@ -250,15 +281,19 @@ class GpuPreprocessor:
             src_len += im.size
             tmp_len += h * OW * 3
         rec = pack_params(params, spec)
-        # one staging buffer: [descs | params | taps | pixels], 256-byte aligned sections
+        # with views, each record's source image follows the records: view_src int32 [n * K]
+        view_src = (np.repeat(np.arange(n, dtype=np.int32), views) if views is not None
+                    else np.empty(0, np.int32))
+        # one staging buffer: [descs | params, view_src | taps | pixels], 256-byte aligned sections
         o_par = _align(desc.nbytes)
-        o_coef = o_par + _align(rec.nbytes)
+        o_coef = o_par + _align(rec.nbytes + view_src.nbytes)
         o_src = o_coef + _align(coef_len * 4)
         total = o_src + src_len + 4  # the resize reads whole dwords of the last row
         stage = torch.empty(total, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
         buf = stage.numpy()
         buf[:desc.nbytes] = desc.view(np.uint8)
         buf[o_par:o_par + rec.nbytes] = rec.view(np.uint8)
+        buf[o_par + rec.nbytes:o_par + rec.nbytes + view_src.nbytes] = view_src.view(np.uint8)
         cv = buf[o_coef:o_coef + coef_len * 4].view(np.int32)
         at = 0
         for t in taps:
@@ -270,10 +305,11 @@ class GpuPreprocessor:
             buf[at:at + im.size] = im.ravel()
             at += im.size
         return _Staged(stage.to(self.device, non_blocking=True), n, o_par, o_coef, o_src,
-                       tmp_len)
+                       tmp_len, views, o_par + rec.nbytes)
 
     def run(self, st):
-        """Device side: resize + augment + normalise a staged batch (4 launches)."""
+        """Device side: resize + augment + normalise a staged batch (4 launches); a batch staged
+        with views gives [n * K, 3, H, W], sample-major (dfu_augment_views)."""
         OH, OW = self.spec.size
         if st.n == 0:
             return torch.empty((0, 3, OH, OW), dtype=torch.float32, device=self.device)
@@ -287,6 +323,18 @@ class GpuPreprocessor:
                                    ctypes.c_void_p(tmp.data_ptr()),
                                    ctypes.c_void_p(resized.data_ptr()), stream),
               "dfu_resize_batch")
+        if st.views is not None:
+            nv = st.n * st.views
+            out = torch.empty((nv, 3, OH, OW), dtype=torch.float32, device=self.device)
+            means = torch.empty(nv, dtype=torch.int32, device=self.device)
+            check(lib.dfu_augment_views(ctypes.c_void_p(resized.data_ptr()), st.n,
+                                        ctypes.c_void_p(base + st.o_par),
+                                        ctypes.c_void_p(base + st.o_view), nv,
+                                        ORDERS[self.spec.order], OH, OW, self._mean, self._std,
+                                        ctypes.c_void_p(means.data_ptr()),
+                                        ctypes.c_void_p(out.data_ptr()), stream),
+                  "dfu_augment_views")
+            return out
         out = torch.empty((st.n, 3, OH, OW), dtype=torch.float32, device=self.device)
         means = torch.empty(st.n, dtype=torch.int32, device=self.device)
         check(lib.dfu_augment_normalize(ctypes.c_void_p(resized.data_ptr()),
@@ -305,6 +353,8 @@ class _Staged:
     o_coef: int
     o_src: int
     tmp_len: int
+    views: int = None      # K parameter records per image (dfu_augment_views), None: one each
+    o_view: int = 0        # view_src int32 [n * K]
 
 
 def decode_rgb(path):
@@ -314,22 +364,32 @@ def decode_rgb(path):
         return np.asarray(im.convert("RGB"))
 
 
+def _check_views(views):
+    if not isinstance(views, int) or views < 1:
+        raise ValueError(f"views = {views!r}: a positive number of views per sample")
+    return views
+
+
 class GpuPairLoader:
     """DataLoader replacement for MultimodalDataset (train_multimodal_fusion.py:259-275): yields
     (rgb, thermal, label) batches already on the GPU, fp32 NCHW as the reference's loader
     produces them after pin_memory + .to(DEVICE).  Decode runs on `num_threads` host threads
     one batch ahead of the GPU; per sample the RGB parameters are drawn before the thermal
-    ones, as __getitem__ applies the two transforms."""
+    ones, as __getitem__ applies the two transforms.  views=K > 1 (test-time augmentation,
+    test_time_augmentation.py:347-361): [B * K, 3, H, W] inputs, view v of sample i in row
+    i * K + v, and [B] labels; per sample and per view the RGB parameters before the thermal
+    ones, the order of the script's nested loops."""
 
     def __init__(self, dataset, batch_size, sampler=None, shuffle=False, train=False,
                  rgb_spec=None, thermal_spec=None, device="cuda", num_threads=4, generator=None,
-                 drop_last=False):
+                 drop_last=False, views=1):
         self.dataset = dataset
         self.batch_size = batch_size
         self.sampler = sampler
         self.shuffle = shuffle
         self.generator = generator
         self.drop_last = drop_last
+        self.views = _check_views(views)
         rgb_spec = rgb_spec or (rgb_train_transform if train else rgb_val_test_transform)
         thermal_spec = thermal_spec or (thermal_train_transform if train
                                         else thermal_val_test_transform)
@@ -377,13 +437,14 @@ class GpuPairLoader:
 
     def _finish(self, rgb, th, labels):
         rp, tp = [], []
-        for _ in labels:
+        for _ in range(len(labels) * self.views):  # sample-major: every view of a sample in turn
             rp.append(sample_params(self.rgb.spec, self.generator) if self.rgb.spec.random
                       else AugParams())
             tp.append(sample_params(self.thermal.spec, self.generator) if self.thermal.spec.random
                       else AugParams())
         y = torch.tensor(labels, dtype=torch.long).to(self.device, non_blocking=True)
-        return self.rgb(rgb, rp), self.thermal(th, tp), y
+        k = self.views if self.views > 1 else None
+        return self.rgb(rgb, rp, k), self.thermal(th, tp, k), y
 
 
 class GpuImageLoader:
@@ -393,16 +454,19 @@ class GpuImageLoader:
     GpuPairLoader.  `spec` defaults to the RGB train / val-test transform of
     train_rgb_only.py:102-118 (the fusion script's RGB transforms, identical); the thermal-only
     script's train transform adds a GaussianBlur this pipeline does not implement, so a thermal
-    loader takes `thermal_val_test_transform` (or a spec without blur)."""
+    loader takes `thermal_val_test_transform` (or a spec without blur).  views=K > 1: [B * K, 3,
+    H, W] images, sample-major, and [B] labels, as GpuPairLoader."""
 
     def __init__(self, dataset, batch_size, sampler=None, shuffle=False, train=False,
-                 spec=None, device="cuda", num_threads=4, generator=None, drop_last=False):
+                 spec=None, device="cuda", num_threads=4, generator=None, drop_last=False,
+                 views=1):
         self.dataset = dataset
         self.batch_size = batch_size
         self.sampler = sampler
         self.shuffle = shuffle
         self.generator = generator
         self.drop_last = drop_last
+        self.views = _check_views(views)
         spec = spec or (rgb_train_transform if train else rgb_val_test_transform)
         self.pre = GpuPreprocessor(spec, device)
         self.device = torch.device(device)
@@ -428,6 +492,6 @@ class GpuImageLoader:
 
     def _finish(self, imgs, labels):
         params = [sample_params(self.pre.spec, self.generator) if self.pre.spec.random
-                  else AugParams() for _ in labels]
+                  else AugParams() for _ in range(len(labels) * self.views)]
         y = torch.tensor(labels, dtype=torch.long).to(self.device, non_blocking=True)
-        return self.pre(imgs, params), y
+        return self.pre(imgs, params, self.views if self.views > 1 else None), y

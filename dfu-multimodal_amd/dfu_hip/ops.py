@@ -967,3 +967,42 @@ def metrics_accumulate(logits, labels, loss, confusion, loss_sum, batches):
     check(lib().dfu_metrics_accumulate(ptr(lg), ptr(labels.contiguous()), rows, C, ptr(lf),
                                        ptr(confusion), ptr(loss_sum), ptr(batches),
                                        stream_ptr()), "dfu_metrics_accumulate")
+
+
+# ------------------------------------------------------ test-time augmentation (csrc/tta.hip)
+def tta_reduce(logits, views):
+    """Per-sample reduction of view logits [samples * views, C], view v of sample i in row
+    i * views + v (dfu_tta_reduce): C == 1 sigmoid, C == 2 softmax[:, 1] and argmax.  Returns
+    (prob fp32 [samples]: mean of the view probabilities; pred int64 [samples]: majority vote of
+    the per-view decisions, a tie is 0)."""
+    lg = logits.detach()
+    if lg.dtype != F32 or not lg.is_contiguous():
+        lg = lg.float().contiguous()
+    rows, C = lg.shape
+    if views < 1 or rows % views:
+        raise ValueError(f"tta_reduce: {rows} rows are not whole samples of {views} views")
+    samples = rows // views
+    prob = torch.empty((samples,), dtype=F32, device=lg.device)
+    pred = torch.empty((samples,), dtype=torch.int64, device=lg.device)
+    if samples:
+        check(lib().dfu_tta_reduce(ptr(lg), samples, views, C, ptr(prob), ptr(pred),
+                                   stream_ptr()), "dfu_tta_reduce")
+    return prob, pred
+
+
+def binary_eval_counts(prob, pred, labels, counts=None):
+    """counts int64 [6] += {tn, fp, fn, tp, greater, ties} (dfu_binary_eval_counts): the
+    confusion counts of pred against labels, and over (label-1 i, label-0 j) pairs the number
+    with prob_i > prob_j / prob_i == prob_j.  A new zeroed vector when counts is None; no host
+    synchronisation."""
+    _req(prob, F32, "binary_eval_counts")
+    n = prob.shape[0]
+    if pred.shape != (n,) or labels.shape != (n,):
+        raise ValueError("binary_eval_counts: prob, pred and labels are [n]")
+    if counts is None:
+        counts = torch.zeros((6,), dtype=torch.int64, device=prob.device)
+    if n:
+        check(lib().dfu_binary_eval_counts(ptr(prob.contiguous()), ptr(pred.long().contiguous()),
+                                           ptr(labels.long().contiguous()), n, ptr(counts),
+                                           stream_ptr()), "dfu_binary_eval_counts")
+    return counts

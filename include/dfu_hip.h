@@ -627,6 +627,42 @@ int dfu_augment_normalize(const uint8_t* img, const dfu_aug_params* params, int3
                           int32_t H, int32_t W, const float* mean3, const float* std3,
                           int32_t* contrast_means, float* out, void* stream);
 
+/* ------------------------------------------------------- test-time augmentation ---- */
+/* The robustness evaluation of notebooks/test_time_augmentation.py: K random views of every
+ * test image through the model, a per-sample mean probability and majority vote (:207-229), and
+ * accuracy / F1 / AUC-ROC / sensitivity / specificity from them (:239-246). */
+/* Order of the flips and the RandomRotation in the Compose (both before ColorJitter and
+ * RandomAffine): the train scripts flip first, the TTA script (:145-167) rotates first. */
+enum dfu_aug_order { DFU_AUG_ORDER_FLIP_ROTATE = 0, DFU_AUG_ORDER_ROTATE_FLIP = 1 };
+/* dfu_augment_normalize producing n_views outputs from n_images resized images: view v applies
+ * params[v] to image view_src[v] (device int32 [n_views]; an index outside [0, n_images) gives
+ * the fill, black, and reads nothing) -> out fp32 [n_views][3][H][W].  contrast_means: n_views
+ * int32 scratch (the contrast mean is per view).  For DFU_AUG_ORDER_ROTATE_FLIP an output pixel
+ * goes affine map -> un-flip -> rotation map -> fetch, fill 0 at each stage as PIL produces it;
+ * with DFU_AUG_ORDER_FLIP_ROTATE and view_src[v] = v this is dfu_augment_normalize, bitwise.
+ * n_views <= 65535. */
+int dfu_augment_views(const uint8_t* img, int32_t n_images, const dfu_aug_params* params,
+                      const int32_t* view_src, int32_t n_views, int32_t order, int32_t H,
+                      int32_t W, const float* mean3, const float* std3, int32_t* contrast_means,
+                      float* out, void* stream);
+/* Per-sample reduction of the view logits, fp32 [samples * views][C], view v of sample i in row
+ * i * views + v.  C == 1 (the TTA script's 1-logit heads, :219-220): p_v = sigmoid(x) in fp32,
+ * vote_v = p_v > 0.5 on the rounded fp32 p_v.  C == 2 (this library's softmax heads):
+ * p_v = softmax(row)[1], vote_v = argmax == 1 (first maximum wins).  prob_out[i] (fp32) = the
+ * sequential fp32 sum of p_v in view order / views; pred_out[i] (int64) = 1 exactly when
+ * 2 * sum(vote_v) > views (:225-228: mean of the votes > 0.5; a tie is 0).  Other C:
+ * DFU_E_INVALID. */
+int dfu_tta_reduce(const float* logits, int32_t samples, int32_t views, int32_t C,
+                   float* prob_out, int64_t* pred_out, void* stream);
+/* counts (device int64 [6], zeroed by the caller) += {tn, fp, fn, tp, greater, ties} of n
+ * samples: the confusion counts of pred != 0 against labels in {0, 1} (other labels are left
+ * out of every count), and over the pairs (label-1 sample i, label-0 sample j) the number with
+ * prob_i > prob_j and with prob_i == prob_j.  AUC-ROC = (greater + ties / 2) / (pos * neg), as
+ * sklearn.metrics.roc_auc_score on tied scores.  Integer atomics: exact and order-independent.
+ * n < 2^24. */
+int dfu_binary_eval_counts(const float* prob, const int64_t* pred, const int64_t* labels,
+                           int32_t n, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
