@@ -322,6 +322,11 @@ int check_desc(const dfu_gemm_desc* d, bool launching, Plan* plan) {
     DFU_CHECK_ARG(d->ldb >= round8(d->N), "dfu_gemm: MN-major B needs ldb >= round8(N)");
   if (d->epilogue == DFU_EPI_BF16_STATS || d->epilogue == DFU_EPI_F32_STATS)
     DFU_CHECK_ARG(d->stats != nullptr, "dfu_gemm: STATS epilogue needs a stats slab");
+  // the split-K / tail-split slabs and the dGELU column sums move as 16-byte vectors
+  DFU_CHECK_ARG(d->workspace == nullptr || ((uintptr_t)d->workspace & 15) == 0,
+                "dfu_gemm: workspace must be 16-byte aligned");
+  DFU_CHECK_ARG(d->epilogue != DFU_EPI_BF16_DGELU || ((uintptr_t)d->stats & 15) == 0,
+                "dfu_gemm: the dGELU column sums (stats) must be 16-byte aligned");
   DFU_CHECK_ARG(d->x3_pairs == 0 || (d->x3_pairs == 1 && d->a_seg > 0 && d->operand_type == 0),
                 "dfu_gemm: x3_pairs (0/1) needs split-pair A (a_seg > 0) and bf16 operands");
   if (d->a_seg) {
@@ -485,6 +490,20 @@ extern "C" int dfu_gemm(const dfu_gemm_desc* d, void* stream) {
   // Strided dgrad: stride^2 phase launches, each a dense stride-1 gather over its live taps
   // (a dense launch would spend (1 - 1/stride^2) of its MFMA work on zero taps).
   const int st = d->conv_stride;
+  // A phase without a live tap is filled by 16-byte vectors (k_phase_fill): checked before the
+  // first phase launches anything
+  for (int ph = 0; ph < st; ++ph)
+    for (int pw = 0; pw < st; ++pw) {
+      const Phase f = make_phase(d, ph, pw);
+      if (f.Hs == 0 || f.Ws == 0 || (f.nr != 0 && f.ns != 0)) continue;
+      DFU_CHECK_ARG(d->epilogue == DFU_EPI_BF16 || d->epilogue == DFU_EPI_BF16_ADD,
+                    "dfu_gemm: strided dgrad supports the BF16 / BF16_ADD epilogues");
+      const bool add = d->epilogue == DFU_EPI_BF16_ADD;
+      DFU_CHECK_ARG(d->ldc % 8 == 0 && ((uintptr_t)d->C & 15) == 0 &&
+                        (!add || (d->ldaux % 8 == 0 && ((uintptr_t)d->aux & 15) == 0)),
+                    "dfu_gemm: a strided dgrad with a tapless phase (stride > R or S) needs C "
+                    "(and aux) 16-byte aligned with ldc (ldaux) %% 8 == 0");
+    }
   for (int ph = 0; ph < st; ++ph)
     for (int pw = 0; pw < st; ++pw) {
       const Phase f = make_phase(d, ph, pw);
@@ -538,8 +557,18 @@ void fill_args(const dfu_gemm_desc* d, const Plan& pl, const Phase* ph, GemmArgs
   a.aux = d->aux; a.ldaux = d->ldaux;
   a.aux_out = d->aux_out; a.ldaux_out = d->ldaux_out;
   a.stats = d->stats;
-  a.n4 = (d->N % 4 == 0 && d->ldc % 4 == 0 && (d->aux == nullptr || d->ldaux % 4 == 0) &&
-          (d->aux_out == nullptr || d->ldaux_out % 4 == 0))
+  // The vector classes need every access of theirs naturally aligned: n4 moves 4 columns of C,
+  // aux and aux_out at once (8 B of 16-bit, 16 B of fp32 elements), so beside N and the leading
+  // dimensions each of those bases is a multiple of 4 of its elements; n8 (16-B merged stores of
+  // 16-bit C / aux_out) also takes their bases at 16 B.  Anything else runs the scalar class.
+  const bool c16 = !(d->epilogue == DFU_EPI_F32 || d->epilogue == DFU_EPI_F32_RESID ||
+                     d->epilogue == DFU_EPI_F32_ACC || d->epilogue == DFU_EPI_PATCH ||
+                     (d->epilogue == DFU_EPI_F32_STATS && d->aux_out == nullptr));
+  const bool aux16 = !(d->epilogue == DFU_EPI_F32_RESID || d->epilogue == DFU_EPI_PATCH);
+  auto aligned = [](const void* p, bool is16) { return ((uintptr_t)p & (is16 ? 7 : 15)) == 0; };
+  a.n4 = (d->N % 4 == 0 && d->ldc % 4 == 0 && aligned(d->C, c16) &&
+          (d->aux == nullptr || (d->ldaux % 4 == 0 && aligned(d->aux, aux16))) &&
+          (d->aux_out == nullptr || (d->ldaux_out % 4 == 0 && aligned(d->aux_out, true))))
              ? 1
              : 0;
   a.n8 = (a.n4 && d->N % 8 == 0 && d->ldc % 8 == 0 && ((uintptr_t)d->C & 15) == 0 &&

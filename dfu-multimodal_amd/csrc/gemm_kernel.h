@@ -88,7 +88,8 @@ struct GemmArgs {
   // each K-step of 64 is [hi | lo] of 32 real k, and the kernel forms the three products.
   int a_seg, a_pix;
   int64_t a_lo_delta;
-  int n4;       // N and every leading dimension % 4 == 0: one vector access per 4 columns
+  int n4;       // N and every leading dimension % 4 == 0, C / aux / aux_out bases aligned to 4
+                // of their elements: one vector access per 4 columns
   int n8;       // N, ldc (, ldaux_out) % 8 == 0 and 16-B aligned bf16 outputs: paired stores
   int ep_tokens;
   // conv geometry

@@ -131,7 +131,8 @@ typedef struct dfu_gemm_desc {
                           10, 11 = 4-wave 256x64, 128x64 at 2/CU (K-contiguous
                           or implicit-conv A, K-contiguous B)                  */
   void* workspace;     /* split-K fp32 slabs (dfu_gemm_workspace_bytes); NULL =  */
-  int64_t workspace_bytes; /*   split-K partials accumulate with fp32 atomics     */
+  int64_t workspace_bytes; /*   split-K partials accumulate with fp32 atomics (the
+                              phased tiles 7-9 have none: DFU_E_INVALID)          */
   /* Split-K with slabs: NULL = a second kernel adds the slabs into C.  Otherwise a zeroed
    * int32[tile_counters_len] the launch returns zeroed: the last of a tile's splits to finish
    * adds all its slabs into C inside the GEMM (same order, bitwise the same result).  One
@@ -156,6 +157,18 @@ typedef struct dfu_gemm_desc {
   int32_t x3_pairs;
 } dfu_gemm_desc;
 
+/* Alignment.  A and B (and a_lo): 16 bytes.  bias: 4.  workspace, and stats with BF16_DGELU: 16.
+ * C, aux and aux_out may sit anywhere their element type allows (e.g. column slices of a wider
+ * row); the epilogue picks its store class from what it is given and never issues a misaligned
+ * vector access:
+ *   - 16-byte merged stores of 16-bit outputs: N, ldc (ldaux_out) % 8 == 0 and C (aux_out) 16-byte
+ *     aligned, and the conditions of the next class;
+ *   - 4-column vectors: N and every leading dimension in use % 4 == 0, and C, aux and aux_out
+ *     each aligned to 4 of its own elements (8 bytes of 16-bit, 16 bytes of fp32 elements);
+ *   - otherwise one access per element (same values, slower).
+ * A strided CONV_DGRAD whose stride exceeds R or S fills its tapless phases with 16-byte
+ * vectors: it needs ldc % 8 == 0 and C 16-byte aligned (BF16_ADD: ldaux and aux as well) and is
+ * refused with DFU_E_INVALID otherwise, before anything is launched. */
 int dfu_gemm(const dfu_gemm_desc* desc, void* stream);
 /* 128-row blocks (rows of the stats slab) produced by DFU_EPI_BF16_STATS for M rows. */
 int dfu_gemm_stats_tiles(int32_t M);

@@ -73,6 +73,19 @@ def test_gemm_validation_errors(kw, msg):
         L.check(rc, "dfu_gemm")
 
 
+@pytest.mark.parametrize("tile", [7, 8])
+def test_gemm_phased_split_k_needs_a_workspace(tile):
+    """Split-K without a workspace is the fp32-atomics path, which the phased tiles do not have:
+    the descriptor is refused in launch(), before any kernel."""
+    lib = L.load()
+    d = _desc(a_mode=L.OPND_MNMAJOR, b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC, split_k=2,
+              tile=tile)
+    assert lib.dfu_gemm_workspace_bytes(ctypes.byref(d)) == 2 * 256 * 256 * 4
+    rc = lib.dfu_gemm(ctypes.byref(d), None)
+    assert rc == L.DFU_E_INVALID
+    assert "phased 256x256 tile needs a workspace" in lib.dfu_last_error_string().decode()
+
+
 def test_x3_pairs_validation_and_plan():
     """Interleaved-pair bf16x3 descriptors (dfu_gemm_desc.x3_pairs): they need split-pair A with
     K = 2 a_seg, a_seg % 32 == 0; the planner picks one of the tiles that instantiate them."""
