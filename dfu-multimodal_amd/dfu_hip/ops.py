@@ -1006,3 +1006,36 @@ def binary_eval_counts(prob, pred, labels, counts=None):
                                            ptr(labels.long().contiguous()), n, ptr(counts),
                                            stream_ptr()), "dfu_binary_eval_counts")
     return counts
+
+
+def binary_curve(prob, labels, out=None):
+    """sklearn's _binary_clf_curve on the device (dfu_binary_curve): returns (thresholds fp32
+    [n], tps int64 [n], fps int64 [n], k int32 [1]); entries [0, k) hold the distinct scores in
+    descending order and the label-1 / label-0 samples scored at or above each, the rest is
+    uninitialised.  Samples with a label outside {0, 1} or a NaN score are left out.  `out`: the
+    caller's (thresholds, tps, fps) buffers of at least n entries.  n == 0 returns empty tensors
+    and k = 0 without a launch; no host synchronisation."""
+    _req(prob, F32, "binary_curve")
+    n = prob.shape[0]
+    if prob.dim() != 1 or labels.shape != (n,):
+        raise ValueError("binary_curve: prob and labels are [n]")
+    if not labels.is_cuda:
+        raise ValueError("binary_curve: tensor must be on the GPU")
+    dev = prob.device
+    if out is None:
+        out = (torch.empty((n,), dtype=F32, device=dev),
+               torch.empty((n,), dtype=torch.int64, device=dev),
+               torch.empty((n,), dtype=torch.int64, device=dev))
+    thresholds, tps, fps = out
+    for t, dt in ((thresholds, F32), (tps, torch.int64), (fps, torch.int64)):
+        _req(t, dt, "binary_curve")
+        if t.dim() != 1 or t.shape[0] < n or not t.is_contiguous():
+            raise ValueError("binary_curve: out buffers are contiguous [>= n]")
+    if not n:
+        return thresholds, tps, fps, torch.zeros((1,), dtype=torch.int32, device=dev)
+    k = torch.empty((1,), dtype=torch.int32, device=dev)
+    ws = torch.empty((3 * n,), dtype=torch.int32, device=dev)  # 12 n bytes (include/dfu_hip.h)
+    check(lib().dfu_binary_curve(ptr(prob.contiguous()), ptr(labels.long().contiguous()), n,
+                                 ptr(thresholds), ptr(tps), ptr(fps), ptr(k), ptr(ws),
+                                 stream_ptr()), "dfu_binary_curve")
+    return thresholds, tps, fps, k

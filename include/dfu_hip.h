@@ -676,6 +676,23 @@ int dfu_tta_reduce(const float* logits, int32_t samples, int32_t views, int32_t 
 int dfu_binary_eval_counts(const float* prob, const int64_t* pred, const int64_t* labels,
                            int32_t n, int64_t* counts, void* stream);
 
+/* ------------------------------------------------------- extended medical metrics ---- */
+/* The curve behind notebooks/extended_metrics.py's roc_curve, precision_recall_curve and auc:
+ * sklearn.metrics._ranking._binary_clf_curve of n samples (prob fp32 [n], labels int64 [n]).
+ * A sample is valid when its label is 0 or 1 and its score is not NaN; an invalid sample is left
+ * out of every count and is never a threshold (as dfu_binary_eval_counts leaves out other
+ * labels).  With K the number of distinct scores (IEEE ==: -0.0 and 0.0 are one score) among the
+ * valid samples: thresholds (fp32 [n]) [0, K) = the distinct scores, strictly descending;
+ * tps (int64 [n]) [r] = the number of valid label-1 samples with prob >= thresholds[r];
+ * fps (int64 [n]) [r] = the same for label 0; k_out (device int32 [1]) = K.  Entries at index
+ * >= K are not written; without a valid sample K = 0 and nothing else is written.
+ * workspace: 12 * n bytes of device memory, 4-byte aligned, contents ignored (the call neither
+ * allocates nor synchronises).  Rank counting, integer arithmetic only: exact and order-
+ * independent, at a cost of n^2 comparisons (test sets hold 1e2 .. 1e4 samples).  0 < n < 2^20;
+ * a null pointer or another n: DFU_E_INVALID. */
+int dfu_binary_curve(const float* prob, const int64_t* labels, int32_t n, float* thresholds,
+                     int64_t* tps, int64_t* fps, int32_t* k_out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
