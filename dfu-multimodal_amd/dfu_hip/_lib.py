@@ -176,6 +176,8 @@ PROTOTYPES = {
     "dfu_tta_reduce": [P, I32, I32, I32, P, P, P],
     "dfu_binary_eval_counts": [P, P, P, I32, P, P],
     "dfu_binary_curve": [P, P, I32, P, P, P, P, P, P],
+    "dfu_image_minmax": [P, I32, I32, P, P],
+    "dfu_cam_overlay": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P, P, F, P, P, P, P],
 }
 _RESTYPE = {"dfu_last_error_string": c_char_p, "dfu_gemm_workspace_bytes": c_int64,
             "dfu_gemm_f32_workspace_bytes": c_int64, "dfu_bn_finalize_ws_bytes": c_int64,

@@ -6,6 +6,7 @@ except where an output is documented as returned; nothing synchronises.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -1039,3 +1040,131 @@ def binary_curve(prob, labels, out=None):
                                  ptr(thresholds), ptr(tps), ptr(fps), ptr(k), ptr(ws),
                                  stream_ptr()), "dfu_binary_curve")
     return thresholds, tps, fps, k
+
+
+# ------------------------------------------ Grad-CAM visualisation (csrc/gradcam_viz.hip)
+def linear_taps(n_in, n_out):
+    """The two source indices and the weight of the second for every output coordinate of a
+    bilinear resize n_in -> n_out with OpenCV's INTER_LINEAR coordinates, in fp64:
+    f = (d + 0.5) * (n_in / n_out) - 0.5, i0 = floor(f), w = fp32(f - i0) (a w that rounds to 1
+    becomes the next sample with weight 0: the same pixel value); below the first
+    sample (i0 < 0) and from the last one on (i0 >= n_in - 1) the index is clamped and w = 0;
+    i1 = min(i0 + 1, n_in - 1).  Returns (i0 int32, i1 int32, w fp32) of length n_out; the
+    identity when n_in == n_out."""
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"linear_taps: {n_in} -> {n_out}")
+    f = (np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5
+    i0 = np.floor(f)
+    w = (f - i0).astype(np.float32)
+    # f a rounding error below an integer: f - i0 rounds to 1.0 in fp32.  The next sample with
+    # weight 0 is the same pixel value and keeps w in [0, 1).
+    carry = w == 1
+    i0[carry] += 1
+    w[carry] = 0
+    low, high = i0 < 0, i0 >= n_in - 1
+    i0 = np.where(low, 0, np.where(high, n_in - 1, i0)).astype(np.int32)
+    w[low | high] = 0
+    return i0, np.minimum(i0 + 1, n_in - 1).astype(np.int32), w
+
+
+def jet_lut():
+    """The default colour table of cam_overlay: uint8 [256, 3], RGB order.  The classic jet
+    ramp 255 * (1.5 - |4 i / 255 - c|) with channel centres c = 3, 2, 1 for R, G, B, clamped to
+    [0, 255] and rounded half to even, in integers: n = 765 - 2 |4 i - 255 c| is odd, so with
+    q = n // 2 the value is q + (q & 1).  Its two ends, (0, 0, 128) and (128, 0, 0), are those
+    of OpenCV's COLORMAP_JET; in between it may differ from OpenCV's table by a level or two
+    (pass cv2's own table as `lut` where that matters)."""
+    i = np.arange(256, dtype=np.int64)[:, None]
+    c = np.array([3, 2, 1], dtype=np.int64)[None, :]
+    q = (765 - 2 * np.abs(4 * i - 255 * c)) // 2
+    return np.clip(q + (q & 1), 0, 255).astype(np.uint8)
+
+
+_VIZ_TABLES = {}  # (device, h, w, H, W) -> the six tap tables; (device, "jet") -> the table
+
+
+def _viz_taps(device, h, w, H, W):
+    key = (device, h, w, H, W)
+    if key not in _VIZ_TABLES:
+        _VIZ_TABLES[key] = tuple(torch.from_numpy(a).to(device)
+                                 for a in linear_taps(w, W) + linear_taps(h, H))
+    return _VIZ_TABLES[key]
+
+
+def _viz_jet(device):
+    key = (device, "jet")
+    if key not in _VIZ_TABLES:
+        _VIZ_TABLES[key] = torch.from_numpy(jet_lut()).to(device)
+    return _VIZ_TABLES[key]
+
+
+def image_minmax(x):
+    """(min, max) of every image of a batch (dfu_image_minmax): x fp32 [B, ...] -> fp32 [B, 2].
+    A NaN in x is outside the contract; no host synchronisation."""
+    _req(x, F32, "image_minmax")
+    if x.dim() < 1:
+        raise ValueError("image_minmax: x is [B, ...]")
+    B = x.shape[0]
+    out = torch.empty((B, 2), dtype=F32, device=x.device)
+    if not B:
+        return out
+    n = x.numel() // B
+    if not n:
+        raise ValueError("image_minmax: empty images")
+    check(lib().dfu_image_minmax(ptr(x.contiguous()), B, n, ptr(out), stream_ptr()),
+          "dfu_image_minmax")
+    return out
+
+
+def cam_overlay(x, cam, alpha=0.5, lut=None, minmax=None, out=None):
+    """The three pictures of the Grad-CAM visualisation for a batch (dfu_cam_overlay): x fp32
+    [B, 3, H, W] (the normalised model input), cam fp32 [B, h, w] in [0, 1] -> (image, heatmap,
+    overlay), uint8 [B, H, W, 3] on the device: the min-max scaled input, the map resampled to
+    H x W (linear_taps) and coloured through `lut` (uint8 [256, 3] RGB on the device; default
+    jet_lut), and clamp(rint(image * (1 - alpha) + heatmap * alpha)).  `minmax`: fp32 [B, 2]
+    instead of image_minmax(x).  `out`: the caller's three contiguous uint8 buffers of at least
+    B * H * W * 3 bytes; the returned tensors are views of them.  The arithmetic is defined in
+    include/dfu_hip.h; agreement with cv2 is unverified.  The tap tables of a (h, w, H, W) and
+    the default table are copied to the device on first use and kept.  No host synchronisation."""
+    _req(x, F32, "cam_overlay: x")
+    _req(cam, F32, "cam_overlay: cam")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"cam_overlay: x is [B, 3, H, W], got {tuple(x.shape)}")
+    B, _, H, W = x.shape
+    if cam.dim() != 3 or cam.shape[0] != B:
+        raise ValueError(f"cam_overlay: cam is [{B}, h, w], got {tuple(cam.shape)}")
+    if cam.device != x.device:
+        raise ValueError("cam_overlay: x and cam are on different devices")
+    h, w = cam.shape[1:]
+    if B and not (H and W and h and w):
+        raise ValueError("cam_overlay: empty image or map")
+    dev, nbytes = x.device, B * H * W * 3
+    if lut is None:
+        lut = _viz_jet(dev)
+    _req(lut, torch.uint8, "cam_overlay: lut")
+    if tuple(lut.shape) != (256, 3) or not lut.is_contiguous() or lut.device != dev:
+        raise ValueError("cam_overlay: lut is a contiguous uint8 [256, 3] on x's device")
+    if minmax is not None:
+        _req(minmax, F32, "cam_overlay: minmax")
+        if tuple(minmax.shape) != (B, 2) or not minmax.is_contiguous() or minmax.device != dev:
+            raise ValueError(f"cam_overlay: minmax is a contiguous fp32 [{B}, 2]")
+    if out is None:
+        out = tuple(torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev) for _ in range(3))
+    if len(out) != 3:
+        raise ValueError("cam_overlay: out is (image, heatmap, overlay)")
+    for t in out:
+        _req(t, torch.uint8, "cam_overlay: out")
+        if t.numel() < nbytes or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"cam_overlay: out buffers are contiguous, >= {nbytes} bytes")
+    views = tuple(t.view(-1)[:nbytes].view(B, H, W, 3) for t in out)
+    if not B:
+        return views
+    x, cam = x.contiguous(), cam.contiguous()
+    if minmax is None:
+        minmax = image_minmax(x)
+    xi0, xi1, xw, yi0, yi1, yw = _viz_taps(dev, h, w, H, W)
+    check(lib().dfu_cam_overlay(ptr(x), ptr(minmax), ptr(cam), B, H, W, h, w, ptr(xi0), ptr(xi1),
+                                ptr(xw), ptr(yi0), ptr(yi1), ptr(yw), ptr(lut), float(alpha),
+                                ptr(views[0]), ptr(views[1]), ptr(views[2]), stream_ptr()),
+          "dfu_cam_overlay")
+    return views

@@ -693,6 +693,41 @@ int dfu_binary_eval_counts(const float* prob, const int64_t* pred, const int64_t
 int dfu_binary_curve(const float* prob, const int64_t* labels, int32_t n, float* thresholds,
                      int64_t* tps, int64_t* fps, int32_t* k_out, void* workspace, void* stream);
 
+/* ------------------------------------------------------ Grad-CAM visualisation ------- */
+/* The pictures of notebooks/grad_cam_visualization.py (:432-462, :485-487) for a batch.  The
+ * script builds them on the host with numpy and OpenCV; OpenCV is not available to this
+ * project, so the arithmetic below is a definition restated from OpenCV's documented behaviour
+ * (INTER_LINEAR's float path, applyColorMap, addWeighted) and agreement with cv2 itself is
+ * unverified.  Every fp32 operation rounds on its own (no fused multiply-add).
+ *
+ * minmax (fp32 [B][2]) = the minimum and maximum of each of B images of n contiguous floats
+ * (n = C * H * W of an NCHW batch).  Two launches: one sets (+inf, -inf), one reduces on a grid
+ * of ceil(n / 4096) x B blocks, each folding its pair into minmax with integer atomic min / max
+ * on the floats' bit patterns (exact, independent of arrival order; the partials are combined
+ * in place, not by a last arriver or the consumer).  A NaN in x is outside the contract (the
+ * result then depends on where it lies).  0 < B <= 65535, n > 0. */
+int dfu_image_minmax(const float* x, int32_t B, int32_t n, float* minmax, void* stream);
+/* x fp32 [B][3][H][W] with its minmax; cam fp32 [B][h][w] with values in [0, 1]; tap tables
+ * xi0 / xi1 (int32 [W], columns of cam; clamped to [0, w)), xw (fp32 [W]) and yi0 / yi1 / yw of
+ * length H for the rows; lut uint8 [256][3] in RGB order.  Outputs uint8 [B][H][W][3]:
+ *   image   = uint8(((x - min) / (max - min)) * 255): one subtraction, one correctly rounded
+ *             division, one multiplication, truncation (:485-487 in fp32 numpy).  An image with
+ *             max == min gives zeros, where the script divides by zero and gets NaN.
+ *   heatmap = lut[uint8(v * 255)], v the bilinear resample of cam, horizontal pass first:
+ *             t_r = cam[r][xi0[X]] * (1 - xw[X]) + cam[r][xi1[X]] * xw[X] for r = yi0[Y], yi1[Y],
+ *             v = t_yi0 * (1 - yw[Y]) + t_yi1 * yw[Y]; uint8() truncates (the index is taken
+ *             modulo 256 for a cam outside [0, 1]).
+ *   overlay = clamp(rint(image * (1 - alpha) + heatmap * alpha), 0, 255) per channel, rint to
+ *             nearest even, 1 - alpha computed once in fp32, each product rounded, then the sum.
+ * One launch writes all three; a thread owns 16 consecutive bytes of each output and stores them
+ * at once when all three pointers are 16-byte aligned (bytewise otherwise, and in the ragged
+ * last chunk).  B * H * W * 3 < 2^31 and B * h * w < 2^31. */
+int dfu_cam_overlay(const float* x, const float* minmax, const float* cam, int32_t B, int32_t H,
+                    int32_t W, int32_t h, int32_t w, const int32_t* xi0, const int32_t* xi1,
+                    const float* xw, const int32_t* yi0, const int32_t* yi1, const float* yw,
+                    const uint8_t* lut, float alpha, uint8_t* image, uint8_t* heatmap,
+                    uint8_t* overlay, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
