@@ -152,3 +152,134 @@ def test_x3_span_holds_only_conv_weights_in_the_fusion_model():
     opt2 = FusedAdamW(ps, lr=1e-4)
     with pytest.warns(UserWarning, match="x3 shadow"):
         opt2.flat.enable_x3()
+
+
+# ------------------------------------------------- derived weight forms follow edits
+BF16 = torch.bfloat16
+
+
+def _form(w, name):
+    """Buffer of form `name` of managed parameter w as it is in memory now (no request, so
+    nothing is re-derived)."""
+    return getattr(w, {"rows": "_dfu_shadow", "f16": "_dfu_shadow16", "x3": "_dfu_shadow_x3",
+                       "T": "_dfu_shadow_T", "F": "_dfu_shadow_F"}[name])
+
+
+def _rows(w):
+    """bf16 [out][in...] rows of w in its storage order (KRSC for channels-last conv weights)."""
+    v = w.detach()
+    if v.dim() == 4:
+        v = v.permute(0, 2, 3, 1)
+    return v.reshape(w.shape[0], -1).to(BF16)
+
+
+def _want_T(w):
+    return _rows(w).t()
+
+
+def _want_F(w):
+    K, C, R, S = w.shape
+    return _rows(w).view(K, R, S, C).flip(1, 2).permute(3, 1, 2, 0)
+
+
+def _random_step(opt, ps, g):
+    opt.zero_grad()
+    for p in ps:
+        p.grad.copy_(torch.randn(p.shape, generator=g).to(DEV))
+    opt.step()
+    torch.cuda.synchronize()
+
+
+def test_transposed_copy_follows_outside_edits():
+    """The transposed bf16 copy of a managed weight equals bf16(w).t() bitwise on its first
+    request, after an in-place edit through the parameter (with the rows shadow), after an
+    optimizer step without a request in between (the batched transpose launch), and after an
+    edit followed by a step with no use in between.  (72, 40) has partial 64x64 transpose tiles
+    in both directions."""
+    from dfu_hip import functional as Fn
+    from dfu_hip.optim import FusedAdamW
+    torch.manual_seed(11)
+    ws = [torch.nn.Parameter(torch.randn(s, device=DEV)) for s in [(128, 64), (72, 40)]]
+    opt = FusedAdamW(ws, lr=1e-2, weight_decay=1e-2)
+    g = torch.Generator(device="cpu").manual_seed(2)
+    for w in ws:
+        assert torch.equal(Fn.weight_bf16_T(w), _want_T(w))
+        with torch.no_grad():
+            w.mul_(0.5)
+        assert torch.equal(Fn.weight_bf16_T(w), _want_T(w))
+        assert torch.equal(_form(w, "rows"), _rows(w))
+        _random_step(opt, ws, g)
+        assert torch.equal(_form(w, "T"), _want_T(w)), "stale after a step"
+        with torch.no_grad():
+            w.mul_(0.5)
+        _random_step(opt, ws, g)
+        assert torch.equal(Fn.weight_bf16_T(w), _want_T(w))
+        assert torch.equal(_form(w, "rows"), _rows(w))
+
+
+def test_flipped_copy_follows_outside_edits():
+    """The flipped, channel-transposed copy of a managed channels-last conv weight equals
+    shadow.view(K,3,3,C).flip(1,2).permute(3,1,2,0), and the shadow bf16(w), on its first
+    request, after an in-place edit through the parameter, on the first request after an
+    optimizer step (the copy is re-derived on use, not in the step), and after an edit
+    followed by a step with no use in between.  (64, 32, 3, 3): K != C."""
+    from dfu_hip import functional as Fn
+    from dfu_hip.optim import FusedAdamW
+    torch.manual_seed(12)
+    ws = [torch.nn.Parameter(torch.randn(s, device=DEV) * 0.05)
+          for s in [(64, 64, 3, 3), (64, 32, 3, 3)]]
+    opt = FusedAdamW(ws, lr=1e-2, weight_decay=1e-2)
+    assert all(Fn.krsc_strided(w) for w in ws)
+    g = torch.Generator(device="cpu").manual_seed(3)
+
+    def check(w):
+        K, C = w.shape[:2]
+        f = Fn.conv_weight_flipped(w).view(C, 3, 3, K)
+        assert torch.equal(_form(w, "rows"), _rows(w))
+        assert torch.equal(f, _form(w, "rows").view(K, 3, 3, C).flip(1, 2).permute(3, 1, 2, 0))
+        assert torch.equal(f, _want_F(w))
+    for w in ws:
+        check(w)
+        with torch.no_grad():
+            w.mul_(0.5)
+        check(w)
+        _random_step(opt, ws, g)
+        check(w)
+        with torch.no_grad():
+            w.mul_(0.5)
+        _random_step(opt, ws, g)
+        check(w)
+
+
+def test_refresh_shadow_after_a_data_edit():
+    """Edits through ``p.data`` bump no version counter: every derived form stays at its old
+    value (the documented contract) until FlatParams.refresh_shadow(), after which each equals
+    the recomputed one on its next request."""
+    from dfu_hip import functional as Fn
+    from dfu_hip import ops
+    from dfu_hip.optim import FusedAdamW
+    torch.manual_seed(13)
+    lin = torch.nn.Linear(64, 128).to(DEV)
+    conv = torch.nn.Conv2d(64, 64, 3, bias=False).to(DEV)
+    opt = FusedAdamW(list(lin.parameters()) + list(conv.parameters()), lr=1e-3)
+    lw, cw = lin.weight, conv.weight
+
+    def forms():
+        return [Fn.weight_bf16_rows(lw), Fn.weight_f16_rows(lw), Fn.weight_bf16_T(lw),
+                Fn.weight_bf16_rows(cw), Fn.conv_weight_x3(cw),
+                Fn.conv_weight_flipped(cw).view(64, 3, 3, 64)]
+
+    def want():
+        x3 = ops.pack_conv_weight_x3(cw.detach().contiguous(), ops.X3_PAIRS).view(64, -1)
+        return [_rows(lw), lw.detach().to(torch.float16), _want_T(lw), _rows(cw), x3,
+                _want_F(cw)]
+    old = [w.clone() for w in want()]
+    for f, w in zip(forms(), old):
+        assert torch.equal(f, w)
+    lw.data.mul_(0.5)
+    cw.data.mul_(0.5)
+    for i, (f, w) in enumerate(zip(forms(), old)):  # stale: nothing saw the edit
+        assert torch.equal(f, w), i
+    opt.flat.refresh_shadow()
+    for i, (f, w) in enumerate(zip(forms(), want())):
+        assert torch.equal(f, w) and not torch.equal(f, old[i]), i
