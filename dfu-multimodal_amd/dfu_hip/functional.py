@@ -405,8 +405,7 @@ _DGRAD_T1X1_MAXC = int(os.environ.get("DFU_DGRAD_T1X1_MAXC", "64"))
 def conv1x1_weight_T(conv, geom):
     """The transposed bf16 shadow [C][K] of a FusedAdamW-managed 1x1 stride-1 conv weight with
     at most _DGRAD_T1X1_MAXC input channels (conv_dgrad's w_t), else None."""
-    if (geom.r == 1 and geom.s == 1 and geom.stride == 1 and geom.pad == 0
-            and geom.c <= _DGRAD_T1X1_MAXC):
+    if geom.plain and geom.c <= _DGRAD_T1X1_MAXC:
         return weight_bf16_T(conv.weight)
     return None
 
@@ -515,12 +514,29 @@ class BNState:
         grads_done(w, b)
 
 
+# --------------------------------------------------------------------------- GEMM patterns
+def gemm_wgrad(N, K, rows, dy, x, dw, ld_dy=None, ld_x=None):
+    """dw[N, K] (fp32) += dy^T x for bf16 dy [rows, N] and x [rows, K], both read MN-major;
+    ld_dy / ld_x: a leading dimension other than N / x's own row stride."""
+    ops.gemm(N, K, rows, dy, N if ld_dy is None else ld_dy, x,
+             x.stride(0) if ld_x is None else ld_x, dw, K, a_mode=L.OPND_MNMAJOR,
+             b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
+
+
+def gemm_dgrad_f32(rows, N, K, dy, w):
+    """fp32 [rows, N] = dy[rows, K] W for the bf16 weight rows W [K][N], read MN-major (the
+    Grad-CAM input gradients, which leave the network in fp32)."""
+    dx = _empty((rows, N), F32, dy.device)
+    ops.gemm(rows, N, K, dy, K, w, N, dx, N, b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32)
+    return dx
+
+
 # --------------------------------------------------------------------------- conv helpers
 def conv_fwd(x_rows, geom, w_krsc, y, stats):
     """y[M, K] = conv(x) for NHWC x with a KRSC bf16 weight; BN tile statistics into stats."""
     g = geom
     M = g.n * g.p * g.q
-    if g.r == 1 and g.s == 1 and g.stride == 1 and g.pad == 0:
+    if g.plain:
         ops.gemm(M, g.k, g.c, x_rows, g.c, w_krsc, g.c, y, g.k, epilogue=L.EPI_BF16_STATS,
                  stats=stats)
     else:
@@ -542,7 +558,7 @@ def conv_fwd_x3(x_pair, geom, w3, y, stats, y_lo=None):
     K3 = g.r * g.s * C3
     xk = dict(x3=True, a_lo=lo, x3_pairs=pairs)
     out = dict(aux_out=y_lo, ldaux_out=g.k if y_lo is not None else 0)
-    if g.r == 1 and g.s == 1 and g.stride == 1 and g.pad == 0:
+    if g.plain:
         ops.gemm(M, g.k, C3, hi, g.c, w3, C3, y, g.k, epilogue=L.EPI_F32_STATS, stats=stats,
                  **xk, **out)
     else:
@@ -558,27 +574,23 @@ def conv_dgrad(dy_rows, geom, w_krsc, dx, add=None, w_flip=None, w_t=None):
     on the transposed [C][K] weight."""
     g = geom
     Mx = g.n * g.h * g.w
-    if w_t is not None and g.r == 1 and g.s == 1 and g.stride == 1 and g.pad == 0:
-        ops.gemm(Mx, g.c, g.k, dy_rows, g.k, w_t, g.k, dx, g.c,
-                 epilogue=L.EPI_BF16_ADD if add is not None else L.EPI_BF16, aux=add,
-                 ldaux=g.c if add is not None else 0)
+    out = dict(epilogue=L.EPI_BF16_ADD if add is not None else L.EPI_BF16, aux=add,
+               ldaux=g.c if add is not None else 0)
+    if w_t is not None and g.plain:
+        ops.gemm(Mx, g.c, g.k, dy_rows, g.k, w_t, g.k, dx, g.c, **out)
         return
     if w_flip is not None and add is None and g.stride == 1:
         gd = ops.ConvGeom(g.n, g.p, g.q, g.k, g.c, g.r, g.s, 1, g.r - 1 - g.pad)
         if (gd.p, gd.q) == (g.h, g.w) and g.r - 1 - g.pad >= 0:
             K = g.r * g.s * g.k
             ops.gemm(Mx, g.c, K, dy_rows, 0, w_flip, K, dx, g.c, a_mode=L.OPND_CONV_FWD,
-                     epilogue=L.EPI_BF16, conv=gd)
+                     conv=gd, **out)
             return
-    epi = L.EPI_BF16_ADD if add is not None else L.EPI_BF16
-    aux, ld_aux = add, (g.c if add is not None else 0)
-    if g.r == 1 and g.s == 1 and g.stride == 1 and g.pad == 0:
-        ops.gemm(Mx, g.c, g.k, dy_rows, g.k, w_krsc, g.c, dx, g.c, b_mode=L.OPND_MNMAJOR,
-                 epilogue=epi, aux=aux, ldaux=ld_aux)
+    if g.plain:
+        ops.gemm(Mx, g.c, g.k, dy_rows, g.k, w_krsc, g.c, dx, g.c, b_mode=L.OPND_MNMAJOR, **out)
     else:
         ops.gemm(Mx, g.c, g.r * g.s * g.k, dy_rows, 0, w_krsc, g.r * g.s * g.c, dx, g.c,
-                 a_mode=L.OPND_CONV_DGRAD, b_mode=L.OPND_CONV_DGRAD_W, epilogue=epi, aux=aux,
-                 ldaux=ld_aux, conv=g)
+                 a_mode=L.OPND_CONV_DGRAD, b_mode=L.OPND_CONV_DGRAD_W, conv=g, **out)
 
 
 def conv_wgrad(dy_rows, x_rows, geom, dw):
@@ -588,25 +600,66 @@ def conv_wgrad(dy_rows, x_rows, geom, dw):
     permute-added into the OIHW gradient."""
     g = geom
     M = g.n * g.p * g.q
-    if g.r == 1 and g.s == 1 and g.stride == 1 and g.pad == 0:
-        ops.gemm(g.k, g.c, M, dy_rows, g.k, x_rows, g.c, dw, g.c, a_mode=L.OPND_MNMAJOR,
-                 b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
+    N = g.r * g.s * g.c
+    wx = dict(a_mode=L.OPND_MNMAJOR, b_mode=L.OPND_CONV_WGRAD_X, epilogue=L.EPI_F32_ACC, conv=g)
+    if g.plain:
+        gemm_wgrad(g.k, g.c, M, dy_rows, x_rows, dw, ld_x=g.c)
     elif krsc_strided(dw):
-        N = g.r * g.s * g.c
-        ops.gemm(g.k, N, M, dy_rows, g.k, x_rows, 0, _rows2d(dw), N, a_mode=L.OPND_MNMAJOR,
-                 b_mode=L.OPND_CONV_WGRAD_X, epilogue=L.EPI_F32_ACC, conv=g)
+        ops.gemm(g.k, N, M, dy_rows, g.k, x_rows, 0, _rows2d(dw), N, **wx)
     else:
-        N = g.r * g.s * g.c
         acc = _empty((g.k, N), F32, dy_rows.device)
         ops.zero_(acc)
-        ops.gemm(g.k, N, M, dy_rows, g.k, x_rows, 0, acc, N, a_mode=L.OPND_MNMAJOR,
-                 b_mode=L.OPND_CONV_WGRAD_X, epilogue=L.EPI_F32_ACC, conv=g)
+        ops.gemm(g.k, N, M, dy_rows, g.k, x_rows, 0, acc, N, **wx)
         ops.conv_grad_krsc_to_oihw(acc, dw)
+
+
+def conv_param_wgrad(conv, dy_rows, x_rows, geom):
+    """conv.weight.grad += wgrad(dy, x), where the weight wants one."""
+    if wants(conv.weight):
+        conv_wgrad(dy_rows, x_rows, geom, grad_buffer(conv.weight))
+        grads_done(conv.weight)
 
 
 def _geom(conv, B, H, W):
     Cout, Cin, R, S = conv.weight.shape
     return ops.ConvGeom(B, H, W, Cin, Cout, R, S, conv.stride[0], conv.padding[0])
+
+
+# ------------------------------------------------------------------ explicit-im2col conv
+# (the ResNet stem's bf16 forward; nn.Conv2d for channel counts the implicit GEMM does not take)
+def im2col_operands(x, w):
+    """-> (fp32 x, bf16 weight rows [Cout][Kp]): K = C*R*S in OIHW order, padded to 16."""
+    Kp = ((w.shape[1] * w.shape[2] * w.shape[3] + 15) // 16) * 16
+    return x.detach().float() if x.dtype != F32 else x.detach(), weight_bf16_rows(w, ld=Kp)
+
+
+def im2col_conv_fwd(xf, wb, g, want_stats):
+    """y[M, K] (bf16) = im2col(x) W^T (+ the BN tile statistics) -> (col, y, stats or None)."""
+    Kp = wb.shape[1]
+    col = ops.im2col_f32(xf, g.r, g.s, g.stride, g.pad, Kp)[0]
+    M = col.shape[0]
+    y = _empty((M, g.k), BF16, xf.device)
+    stats = _empty((ops.stats_tiles(M), 2, g.k), F32, xf.device) if want_stats else None
+    ops.gemm(M, g.k, Kp, col, Kp, wb, Kp, y, g.k,
+             epilogue=L.EPI_BF16_STATS if want_stats else L.EPI_BF16, stats=stats)
+    return col, y, stats
+
+
+def im2col_conv_wgrad(dy, col, w, g):
+    """w.grad += dY^T col over the forward's bf16 im2col rows (any row stride: the hi rows of a
+    bf16x3 split pair too), where w wants a gradient."""
+    if wants(w):
+        K = g.c * g.r * g.s
+        gemm_wgrad(g.k, K, g.n * g.p * g.q, dy, col, grad_buffer(w).view(g.k, K))
+        grads_done(w)
+
+
+def im2col_conv_dx(dy, wb, g):
+    """fp32 NCHW input gradient (the Grad-CAM path, grad_cam_visualization.py:374): fp32
+    dcol = dY W (MFMA GEMM), then its col2im adjoint (a gather kernel)."""
+    Kp = wb.shape[1]
+    dcol = gemm_dgrad_f32(g.n * g.p * g.q, Kp, g.k, dy, wb)
+    return ops.col2im_f32(dcol, g.n, g.c, g.h, g.w, g.r, g.s, g.stride, g.pad, g.p, g.q, Kp)
 
 
 # ------------------------------------------------------------------------------- stem
@@ -617,105 +670,82 @@ class StemFn(torch.autograd.Function):
     """conv1 7x7/s2/p3 (3->64, explicit bf16 im2col, K padded 147->160) + bn1 + relu +
     maxpool 3x3/s2/p1.  Input fp32 (B,3,H,W) any strides; output bf16 channels_last."""
 
-    KP = 160
-
     @staticmethod
     def forward(ctx, x, w, gamma, beta, mod):
-        conv, bn = mod.conv1, mod.bn1
-        B, C, H, W = x.shape
-        R = S = conv.weight.shape[2]
-        st, pad = conv.stride[0], conv.padding[0]
-        Kp = ((C * R * S + 15) // 16) * 16
-        xf = x.detach().float() if x.dtype != F32 else x.detach()
-        wb = weight_bf16_rows(w, ld=Kp)
-        Cout = w.shape[0]
+        B, _, H, W = x.shape
+        g = _geom(mod.conv1, B, H, W)
+        xf, wb = im2col_operands(x, w)
         x3 = _x3(mod)
-        # bf16x3: one implicit-GEMM kernel (dfu_stem_conv_x3: no pair im2col in HBM) where its
-        # geometry allows; DFU_STEM_FUSED=0: the pair im2col + interleaved-pair GEMM (A/B)
-        fused = x3 and _STEM_FUSED and Kp == 160 and ops.stem_conv_x3_ok(xf, w, st, pad)
-        if fused:  # no im2col rows: the backward's weight gradient reads x (dfu_stem_wgrad_x3)
-            y, y_lo, stats, col, P, Q = ops.stem_conv_x3(xf, w.detach(), st, pad, want_col=False)
-        elif x3:
-            (col, col_lo), P, Q = ops.im2col_f32_x3(xf, R, S, st, pad, Kp)  # split pair
-        else:
-            col, P, Q = ops.im2col_f32(xf, R, S, st, pad, Kp)
-        M = B * P * Q
-        if not fused:
-            y = _empty((M, Cout), BF16, x.device)
-            stats = _empty((ops.stats_tiles(M), 2, Cout), F32, x.device)
-        bns = BNState(bn, M, Cout, x.device)
-        if x3:
-            a = _empty((M * Cout // 8,), torch.uint8, x.device)  # bn1's ReLU bitmask
-            if not fused:
-                y_lo = _empty((M, Cout), BF16, x.device)  # the conv output as a split pair
-                if _X3_PAIRS and Kp % 32 == 0:  # interleaved pairs (conv_weight_x3)
-                    w3, K3, pairs = ops.split_x3(w.detach().reshape(Cout, -1), ops.X3_PAIRS,
-                                                 seg=Kp), 2 * Kp, True
-                else:
-                    w3, K3, pairs = weight_x3_rows(w, seg=Kp), 3 * Kp, False
-                ops.gemm(M, Cout, K3, col, Kp, w3, K3, y, Cout, epilogue=L.EPI_F32_STATS,
-                         stats=stats, x3=True, a_lo=col_lo, x3_pairs=pairs, aux_out=y_lo,
-                         ldaux_out=Cout)
-                del col_lo
-            bns.forward_coeffs(stats)
-            # bn1 + ReLU applied inside the pool, from the pair (no fp32 BN output stored)
-            out_lo, out, am, P2, Q2 = ops.maxpool_bn_fwd_x3(y, y_lo, bns.scale, bns.shift, B, P,
-                                                            Q, Cout, relu_mask=a)
-            del y_lo
-        else:
-            ops.gemm(M, Cout, Kp, col, Kp, wb, Kp, y, Cout, epilogue=L.EPI_BF16_STATS,
-                     stats=stats)
-            bns.forward_coeffs(stats)
-            # bn1 + relu applied inside the pool (the backward recomputes the ReLU mask from
-            # y, so the BN output itself is never stored)
-            a = None
-            out, am, P2, Q2 = ops.maxpool_fwd(y, B, P, Q, Cout, scale=bns.scale,
-                                              shift=bns.shift)
-        ctx.mod = mod
-        ctx.bns = bns
-        ctx.x3 = x3
-        ctx.dims = (B, C, H, W, P, Q, P2, Q2, Cout, Kp, R, S, st, pad)
+        body = StemFn._forward_x3 if x3 else StemFn._forward_bf16
+        out, out_lo, ctx.bns, src, y, a, am = body(xf, w, wb, mod.bn1, g)
+        ctx.mod, ctx.x3, ctx.geo = mod, x3, g
+        ctx.pooled = out.shape[1:3]
         ctx.x_requires_grad = x.requires_grad
-        ctx.fused = fused
-        ctx.save_for_backward(xf if fused else col, y, a, am, wb)
+        ctx.fused = src is xf
+        ctx.save_for_backward(src, y, a, am, wb)
         res = out.permute(0, 3, 1, 2)
-        if x3:
+        if out_lo is not None:
             res._dfu_lo = out_lo
         return res
 
+    # Both bodies return (out [B, P2, Q2, C], out_lo or None, BN state, src, y, a, am): `src` is
+    # what the weight gradient reads (im2col rows; x itself after the fused conv), `a` the mask.
+    @staticmethod
+    def _forward_bf16(xf, w, wb, bn, g):
+        col, y, stats = im2col_conv_fwd(xf, wb, g, True)
+        bns = BNState(bn, y.shape[0], g.k, xf.device)
+        bns.forward_coeffs(stats)
+        # bn1 + relu applied inside the pool (the backward recomputes the ReLU mask from y, so
+        # the BN output itself is never stored)
+        out, am, _, _ = ops.maxpool_fwd(y, g.n, g.p, g.q, g.k, scale=bns.scale, shift=bns.shift)
+        return out, None, bns, col, y, None, am
+
+    @staticmethod
+    def _forward_x3(xf, w, wb, bn, g):
+        M, Cout, st, pad, Kp, dev = g.n * g.p * g.q, g.k, g.stride, g.pad, wb.shape[1], xf.device
+        # one implicit-GEMM kernel (dfu_stem_conv_x3: no pair im2col in HBM) where its geometry
+        # allows; DFU_STEM_FUSED=0: the pair im2col + interleaved-pair GEMM (A/B)
+        fused = _STEM_FUSED and Kp == 160 and ops.stem_conv_x3_ok(xf, w, st, pad)
+        if fused:  # no im2col rows: the backward's weight gradient reads x (dfu_stem_wgrad_x3)
+            y, y_lo, stats = ops.stem_conv_x3(xf, w.detach(), st, pad, want_col=False)[:3]
+        else:
+            col, col_lo = ops.im2col_f32_x3(xf, g.r, g.s, st, pad, Kp)[0]  # split pair
+            y = _empty((M, Cout), BF16, dev)
+            y_lo = _empty((M, Cout), BF16, dev)  # the conv output as a split pair
+            stats = _empty((ops.stats_tiles(M), 2, Cout), F32, dev)
+            if _X3_PAIRS and Kp % 32 == 0:  # interleaved pairs (conv_weight_x3)
+                w3, K3, pairs = ops.split_x3(w.detach().reshape(Cout, -1), ops.X3_PAIRS,
+                                             seg=Kp), 2 * Kp, True
+            else:
+                w3, K3, pairs = weight_x3_rows(w, seg=Kp), 3 * Kp, False
+            ops.gemm(M, Cout, K3, col, Kp, w3, K3, y, Cout, epilogue=L.EPI_F32_STATS,
+                     stats=stats, x3=True, a_lo=col_lo, x3_pairs=pairs, aux_out=y_lo,
+                     ldaux_out=Cout)
+            del col_lo
+        bns = BNState(bn, M, Cout, dev)
+        bns.forward_coeffs(stats)
+        a = _empty((M * Cout // 8,), torch.uint8, dev)  # bn1's ReLU bitmask
+        # bn1 + ReLU applied inside the pool, from the pair (no fp32 BN output stored)
+        out_lo, out, am, _, _ = ops.maxpool_bn_fwd_x3(y, y_lo, bns.scale, bns.shift, g.n, g.p,
+                                                      g.q, Cout, relu_mask=a)
+        return out, out_lo, bns, xf if fused else col, y, a, am
+
     @staticmethod
     def backward(ctx, gout):
-        col, y, a, am, wb = ctx.saved_tensors
-        B, C, H, W, P, Q, P2, Q2, Cout, Kp, R, S, st, pad = ctx.dims
-        mod = ctx.mod
-        g = rows_view(nhwc_bf16(gout))
-        da = ops.maxpool_bwd(g, am, B, P, Q, Cout, P2, Q2).view(B * P * Q, Cout)
-        M = B * P * Q
+        src, y, a, am, wb = ctx.saved_tensors
+        g = ctx.geo
+        da = ops.maxpool_bwd(rows_view(nhwc_bf16(gout)), am, g.n, g.p, g.q, g.k,
+                             *ctx.pooled).view(y.shape)
         dy = torch.empty_like(y)
-        if ctx.x3:  # the forward's own ReLU bitmask (its pre-activation was fp32)
-            ctx.bns.backward(da, y, a, 3, dy, None)
-        else:
-            ctx.bns.backward(da, y, None, 2, dy, None)
-        w = mod.conv1.weight
-        if wants(w):
-            dw = grad_buffer(w).view(Cout, -1)
-            K = C * R * S
-            if ctx.fused:  # from x itself (the saved tensor is xf): no im2col rows
-                ops.stem_wgrad_x3(col, dy, dw, st, pad)
-            else:
-                # bf16 im2col rows: the col itself, or the hi rows of the bf16x3 split pair
-                ops.gemm(Cout, K, M, dy, Cout, col, col.stride(0), dw, K, a_mode=L.OPND_MNMAJOR,
-                         b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
+        # bf16x3: the forward's own ReLU bitmask `a` (its pre-activation was fp32)
+        ctx.bns.backward(da, y, a, 3 if ctx.x3 else 2, dy, None)
+        w = ctx.mod.conv1.weight
+        if not ctx.fused:  # over the bf16 im2col rows (bf16x3: the hi rows of the split pair)
+            im2col_conv_wgrad(dy, src, w, g)
+        elif wants(w):  # from x itself (the saved tensor is xf): no im2col rows
+            ops.stem_wgrad_x3(src, dy, grad_buffer(w).view(g.k, -1), g.stride, g.pad)
             grads_done(w)
-        dx = None
-        if ctx.x_requires_grad:
-            # Grad-CAM path (grad_cam_visualization.py:374): fp32 dcol = dy W (MFMA GEMM),
-            # then its col2im adjoint (a gather kernel) -> fp32 NCHW input gradient.
-            wkn = wb  # [Cout][Kp] viewed as B[k=cout][n=kp]
-            dcol = _empty((M, Kp), F32, y.device)
-            ops.gemm(M, Kp, Cout, dy, Cout, wkn, Kp, dcol, Kp, b_mode=L.OPND_MNMAJOR,
-                     epilogue=L.EPI_F32)
-            dx = ops.col2im_f32(dcol, B, C, H, W, R, S, st, pad, P, Q, Kp)
+        dx = im2col_conv_dx(dy, wb, g) if ctx.x_requires_grad else None
         return dx, None, None, None, None
 
 
@@ -725,6 +755,43 @@ def _fire_grad_hooks(probe, grad):
     gradient the fused backward computed for the tensor it stands for."""
     for hook in list((probe._backward_hooks or {}).values()):
         hook(grad)
+
+
+def conv_bn(xrows, geom, w, bnmod, relu, residual=None, mask=None):
+    """bf16 conv + BN (+ residual) (+ ReLU, its bitmask into `mask`) -> (y, out, BN state)."""
+    dev = xrows.device
+    M = geom.n * geom.p * geom.q
+    y = _empty((M, geom.k), BF16, dev)
+    stats = _empty((ops.stats_tiles(M), 2, geom.k), F32, dev)
+    conv_fwd(xrows, geom, w, y, stats)
+    st = BNState(bnmod, M, geom.k, dev)
+    st.forward_coeffs(stats)
+    out = _empty((M, geom.k), BF16, dev)
+    ops.bn_apply(y, st.scale, st.shift, residual, relu, out, M, geom.k, mask=mask)
+    return y, out, st
+
+
+def conv_bn_x3(xpair, geom, w3x, bnmod, relu, res=None, res_mode=0, want_pair=True,
+               want_f32=False):
+    """bf16x3: fp32 conv + BN (+res) (+ReLU) -> (y bf16, out bf16 (hi), out lo, out fp32, BN
+    state, ReLU bitmask); res_mode 2: res is a split pair."""
+    dev = xpair[0].device
+    M = geom.n * geom.p * geom.q
+    # the conv output as a split pair: y (= bf16(y), what the BN backward reads) + y_lo
+    y = _empty((M, geom.k), BF16, dev)
+    y_lo = _empty((M, geom.k), BF16, dev)
+    stats = _empty((ops.stats_tiles(M), 2, geom.k), F32, dev)
+    conv_fwd_x3(xpair, geom, w3x, y, stats, y_lo=y_lo)
+    st = BNState(bnmod, M, geom.k, dev)
+    st.forward_coeffs(stats)
+    out = _empty((M, geom.k), BF16, dev) if want_pair else None
+    lo = _empty((M, geom.k), BF16, dev) if want_pair else None
+    of = _empty((M, geom.k), F32, dev) if want_f32 else None
+    rhi, rlo = res if res_mode == 2 else (res, None)
+    mask = _empty((M * geom.k // 8,), torch.uint8, dev) if relu else None
+    ops.bn_apply_x3(y, st.scale, st.shift, rhi, res_mode, relu, M, geom.k, out_lo=lo,
+                    out_bf16=out, out_f32=of, residual_lo=rlo, y_lo=y_lo, relu_mask=mask)
+    return y, out, lo, of, st, mask
 
 
 class BottleneckFn(torch.autograd.Function):
@@ -738,163 +805,117 @@ class BottleneckFn(torch.autograd.Function):
         xin3 = _take_x3(x) if x3mode else None
         x = nhwc_bf16(x.detach())
         B, Cin, H, W = x.shape
-        dev = x.device
         xr = rows_view(x)
         g1 = _geom(mm["conv1"], B, H, W)
         g2 = _geom(mm["conv2"], B, g1.p, g1.q)
         g3 = _geom(mm["conv3"], B, g2.p, g2.q)
+        down = mm.get("downsample")
+        geo = (g1, g2, g3, _geom(down[0], B, H, W) if down is not None else None)
+        # the backward's weight operands, in both modes (wd: the bodies, before its conv)
         w1 = conv_weight_bf16(mm["conv1"].weight)
         w2 = conv_weight_bf16(mm["conv2"].weight)
         w3 = conv_weight_bf16(mm["conv3"].weight)
-        M1 = B * g1.p * g1.q
-        M2 = B * g2.p * g2.q
-        planes, outc = g1.k, g3.k
-
-        def conv_bn(xrows, geom, w, bnmod, relu, residual=None, mask=None):
-            M = geom.n * geom.p * geom.q
-            y = _empty((M, geom.k), BF16, dev)
-            stats = _empty((ops.stats_tiles(M), 2, geom.k), F32, dev)
-            conv_fwd(xrows, geom, w, y, stats)
-            st = BNState(bnmod, M, geom.k, dev)
-            st.forward_coeffs(stats)
-            out = _empty((M, geom.k), BF16, dev)
-            ops.bn_apply(y, st.scale, st.shift, residual, relu, out, M, geom.k, mask=mask)
-            return y, out, st
-
-        def conv_bn_x3(xpair, geom, w3x, bnmod, relu, res=None, res_mode=0, want_pair=True,
-                       want_f32=False):
-            """bf16x3: fp32 conv + BN (+res) (+ReLU) -> (y bf16, out bf16 (hi), out lo, out
-            fp32, BN state, ReLU bitmask); res_mode 2: res is a split pair."""
-            M = geom.n * geom.p * geom.q
-            # the conv output as a split pair: y (= bf16(y), what the BN backward reads) + y_lo
-            y = _empty((M, geom.k), BF16, dev)
-            y_lo = _empty((M, geom.k), BF16, dev)
-            stats = _empty((ops.stats_tiles(M), 2, geom.k), F32, dev)
-            conv_fwd_x3(xpair, geom, w3x, y, stats, y_lo=y_lo)
-            st = BNState(bnmod, M, geom.k, dev)
-            st.forward_coeffs(stats)
-            out = _empty((M, geom.k), BF16, dev) if want_pair else None
-            lo = _empty((M, geom.k), BF16, dev) if want_pair else None
-            of = _empty((M, geom.k), F32, dev) if want_f32 else None
-            rhi, rlo = res if res_mode == 2 else (res, None)
-            mask = _empty((M * geom.k // 8,), torch.uint8, dev) if relu else None
-            ops.bn_apply_x3(y, st.scale, st.shift, rhi, res_mode, relu, M, geom.k, out_lo=lo,
-                            out_bf16=out, out_f32=of, residual_lo=rlo, y_lo=y_lo, relu_mask=mask)
-            return y, out, lo, of, st, mask
-
-        out_lo = None
-        masks = None
-        if x3mode:
-            y1, a1, a1_lo, _, s1, m1 = conv_bn_x3(xin3, g1, conv_weight_x3(mm["conv1"].weight),
-                                                   mm["bn1"], True)
-            y2, a2, a2_lo, _, s2, m2 = conv_bn_x3((a1, a1_lo), g2,
-                                                   conv_weight_x3(mm["conv2"].weight), mm["bn2"],
-                                                   True)
-            masks = (m1, m2)  # the BN + ReLU backward's masks (the pre-activations were fp32)
-            del a1_lo
-        else:
-            y1, a1, s1 = conv_bn(xr, g1, w1, mm["bn1"], True)
-            y2, a2, s2 = conv_bn(a1, g2, w2, mm["bn2"], True)
-        if mm.get("downsample") is not None:
-            dconv, dbn = mm.get("downsample")[0], mm.get("downsample")[1]
-            gd = _geom(dconv, B, H, W)
-            wd = conv_weight_bf16(dconv.weight)
-            if x3mode:
-                yd, _, _, idn, sd, _ = conv_bn_x3(xin3, gd, conv_weight_x3(dconv.weight), dbn,
-                                                  False, want_pair=False, want_f32=True)
-                res, res_mode = idn, 1
-            else:
-                yd, idn, sd = conv_bn(xr, gd, wd, dbn, False)
-        else:
-            gd = wd = yd = sd = None
-            idn = xr
-            res, res_mode = xin3, 2
-        if x3mode:
-            y3, out, out_lo, _, s3, mask3 = conv_bn_x3((a2, a2_lo), g3,
-                                                        conv_weight_x3(mm["conv3"].weight),
-                                                        mm["bn3"], True, res=res,
-                                                        res_mode=res_mode)
-            del a2_lo, res, xin3
-        else:
-            # bn3 + residual + ReLU also writes its ReLU bitmask: the backward reads M*C/8 bytes
-            # instead of the block output twice (reduce and apply)
-            mask3 = _empty((M2 * outc // 8,), torch.uint8, dev)
-            y3, out, s3 = conv_bn(a2, g3, w3, mm["bn3"], True, residual=idn, mask=mask3)
-        ctx.x3 = x3mode
-        ctx.mod = mod
-        ctx.geo = (g1, g2, g3, gd)
-        ctx.bns = (s1, s2, s3, sd)
-        ctx.shape = (B, Cin, H, W)
+        rec = (BottleneckFn._forward_x3(mm, xin3, geo) if x3mode else
+               BottleneckFn._forward_bf16(mm, xr, geo, w1, w2, w3))
+        (y1, y2, y3, yd), (a1, a2), ctx.bns, (m1, m2, mask3), wd, out, out_lo = rec
+        ctx.x3, ctx.mod, ctx.geo, ctx.shape = x3mode, mod, geo, (B, Cin, H, W)
         ctx.x_requires_grad = ctx.needs_input_grad[0]
         ctx.probes = None
         if getattr(mod, "_probe", False):
             # Hooked `relu` (Grad-CAM): torchvision calls it after bn1 and bn2 as well, so hand
             # the block the two inner ReLU outputs as leaf tensors whose gradient hooks
             # backward fires with da2 / da1 (models/resnet.py Bottleneck.forward).
-            ctx.probes = (from_rows(a1, B, g1.p, g1.q, planes).detach().requires_grad_(True),
-                          from_rows(a2, B, g2.p, g2.q, planes).detach().requires_grad_(True))
+            ctx.probes = (from_rows(a1, B, g1.p, g1.q, g1.k).detach().requires_grad_(True),
+                          from_rows(a2, B, g2.p, g2.q, g1.k).detach().requires_grad_(True))
             mod._probes = ctx.probes
-        ctx.masks = masks
-        ctx.save_for_backward(xr, y1, a1, y2, a2, y3, mask3, w1, w2,
-                              w3, *( (yd, wd) if yd is not None else ()))
-        res = from_rows(out, B, g3.p, g3.q, outc)
+        ctx.masks = (m1, m2)  # bn1 / bn2 + ReLU bitmasks (bf16x3), or None: recomputed from y
+        ctx.save_for_backward(xr, y1, a1, y2, a2, y3, mask3, w1, w2, w3, yd, wd)
+        res = from_rows(out, B, g3.p, g3.q, g3.k)
         if out_lo is not None:
             res._dfu_lo = out_lo
         return res
 
+    # Both bodies return ((y1, y2, y3, yd), (a1, a2), (s1, s2, s3, sd), (m1, m2, mask3), wd, out,
+    # out_lo): wd the downsample conv's bf16 weight (yd, sd, wd: None without that branch).
+    @staticmethod
+    def _forward_bf16(mm, xr, geo, w1, w2, w3):
+        g1, g2, g3, gd = geo
+        y1, a1, s1 = conv_bn(xr, g1, w1, mm["bn1"], True)
+        y2, a2, s2 = conv_bn(a1, g2, w2, mm["bn2"], True)
+        wd, yd, sd, idn = None, None, None, xr  # the identity shortcut
+        if gd is not None:
+            dconv, dbn = mm["downsample"][0], mm["downsample"][1]
+            wd = conv_weight_bf16(dconv.weight)
+            yd, idn, sd = conv_bn(xr, gd, wd, dbn, False)
+        # bn3 + residual + ReLU also writes its ReLU bitmask: the backward reads M*C/8 bytes
+        # instead of the block output twice (reduce and apply)
+        mask3 = _empty((y2.shape[0] * g3.k // 8,), torch.uint8, xr.device)
+        y3, out, s3 = conv_bn(a2, g3, w3, mm["bn3"], True, residual=idn, mask=mask3)
+        return (y1, y2, y3, yd), (a1, a2), (s1, s2, s3, sd), (None, None, mask3), wd, out, None
+
+    @staticmethod
+    def _forward_x3(mm, xin3, geo):
+        g1, g2, g3, gd = geo
+        y1, a1, a1_lo, _, s1, m1 = conv_bn_x3(xin3, g1, conv_weight_x3(mm["conv1"].weight),
+                                               mm["bn1"], True)
+        y2, a2, a2_lo, _, s2, m2 = conv_bn_x3((a1, a1_lo), g2,
+                                               conv_weight_x3(mm["conv2"].weight), mm["bn2"], True)
+        del a1_lo
+        wd, yd, sd, res, res_mode = None, None, None, xin3, 2  # the identity shortcut (a pair)
+        if gd is not None:
+            dconv, dbn = mm["downsample"][0], mm["downsample"][1]
+            wd = conv_weight_bf16(dconv.weight)
+            yd, _, _, res, sd, _ = conv_bn_x3(xin3, gd, conv_weight_x3(dconv.weight), dbn, False,
+                                              want_pair=False, want_f32=True)
+            res_mode = 1
+        # the BN + ReLU backward reads the masks (the pre-activations were fp32)
+        y3, out, out_lo, _, s3, mask3 = conv_bn_x3((a2, a2_lo), g3,
+                                                    conv_weight_x3(mm["conv3"].weight), mm["bn3"],
+                                                    True, res=res, res_mode=res_mode)
+        return (y1, y2, y3, yd), (a1, a2), (s1, s2, s3, sd), (m1, m2, mask3), wd, out, out_lo
+
     @staticmethod
     def backward(ctx, gout):
-        saved = ctx.saved_tensors
-        xr, y1, a1, y2, a2, y3, out, w1, w2, w3 = saved[:10]
-        yd, wd = (saved[10], saved[11]) if len(saved) > 10 else (None, None)
-        mod = ctx.mod
-        mm = mod._modules
+        xr, y1, a1, y2, a2, y3, mask3, w1, w2, w3, yd, wd = ctx.saved_tensors
+        mm = ctx.mod._modules
         g1, g2, g3, gd = ctx.geo
         s1, s2, s3, sd = ctx.bns
         B, Cin, H, W = ctx.shape
-        dev = xr.device
         g = rows_view(nhwc_bf16(gout))
-        M1, M2 = y1.shape[0], y3.shape[0]
-
-        def wgrad(conv, dy, x, geom):
-            if wants(conv.weight):
-                conv_wgrad(dy, x, geom, grad_buffer(conv.weight))
-                grads_done(conv.weight)
-
         # bn3 (+ residual) + relu: the ReLU bitmask its forward apply wrote
         dy3 = torch.empty_like(y3)
         dres = torch.empty_like(y3)
-        s3.backward(g, y3, out, 3, dy3, dres)
+        s3.backward(g, y3, mask3, 3, dy3, dres)
         # downsample branch (its dgrad is added in place after conv1's, below)
         dyd = None
         if yd is not None:
             dyd = torch.empty_like(yd)
             sd.backward(dres, yd, None, False, dyd, None)
-            wgrad(mm.get("downsample")[0], dyd, xr, gd)
+            conv_param_wgrad(mm.get("downsample")[0], dyd, xr, gd)
         # conv3
         da2 = torch.empty_like(a2)
         conv_dgrad(dy3, g3, w3, da2, w_t=conv1x1_weight_T(mm["conv3"], g3))
         if ctx.probes is not None:
             _fire_grad_hooks(ctx.probes[1], from_rows(da2, B, g2.p, g2.q, g2.k))
-        wgrad(mm["conv3"], dy3, a2, g3)
+        conv_param_wgrad(mm["conv3"], dy3, a2, g3)
         # bn2 + relu, conv2
         # BN + ReLU masks: recomputed from y (bf16), or in bf16x3 mode (fp32 pre-activations)
         # the bitmasks the forward apply wrote
         dy2 = torch.empty_like(y2)
-        m1, m2 = ctx.masks if ctx.masks is not None else (None, None)
+        m1, m2 = ctx.masks
         s2.backward(da2, y2, m2, 3 if ctx.x3 else 2, dy2, None)
         da1 = torch.empty_like(a1)
         conv_dgrad(dy2, g2, w2, da1, w_flip=None if g2.stride != 1 else
                    conv_weight_flipped(mm["conv2"].weight))
         if ctx.probes is not None:
             _fire_grad_hooks(ctx.probes[0], from_rows(da1, B, g1.p, g1.q, g1.k))
-        wgrad(mm["conv2"], dy2, a1, g2)
+        conv_param_wgrad(mm["conv2"], dy2, a1, g2)
         # bn1 + relu, conv1 (+ identity gradient fused in the dgrad epilogue)
         dy1 = torch.empty_like(y1)
         s1.backward(da1, y1, m1, 3 if ctx.x3 else 2, dy1, None)
         dx = None
         if ctx.x_requires_grad:
-            dxr = _empty((M1, Cin), BF16, dev)
+            dxr = _empty((y1.shape[0], Cin), BF16, xr.device)
             w1t = conv1x1_weight_T(mm["conv1"], g1)
             if dyd is None:  # identity shortcut: its gradient rides in conv1's dgrad epilogue
                 conv_dgrad(dy1, g1, w1, dxr, add=dres, w_t=w1t)
@@ -903,7 +924,7 @@ class BottleneckFn(torch.autograd.Function):
                 conv_dgrad(dyd, gd, wd, dxr, add=dxr,
                            w_t=conv1x1_weight_T(mm.get("downsample")[0], gd))
             dx = from_rows(dxr, B, H, W, Cin)
-        wgrad(mm["conv1"], dy1, xr, g1)
+        conv_param_wgrad(mm["conv1"], dy1, xr, g1)
         n_params = len(ctx.needs_input_grad) - 2
         return (dx,) + (None,) * n_params + (None,)
 
@@ -976,18 +997,13 @@ class PatchEmbedFn(torch.autograd.Function):
                                    grad_buffer(pos) if wants(pos) else None,
                                    grad_buffer(b) if wants(b) else None)
         if wants(w):
-            dw = grad_buffer(w).view(D, K)
-            ops.gemm(D, K, B * T, gpatch, D, patches, patches.stride(0), dw, K,
-                     a_mode=L.OPND_MNMAJOR, b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
+            gemm_wgrad(D, K, B * T, gpatch, patches, grad_buffer(w).view(D, K))
         grads_done(w, b, cls, pos)
         dx = None
         if ctx.x_requires_grad:
             # Grad-CAM input saliency (grad_cam_visualization.py:374, 401-413): fp32
             # d patches = gpatch W (MFMA GEMM), then the unpatchify permutation.
-            dpatch = _empty((B * T, K), F32, gX.device)
-            ops.gemm(B * T, K, D, gpatch, D, wb, K, dpatch, K, b_mode=L.OPND_MNMAJOR,
-                     epilogue=L.EPI_F32)
-            dx = ops.unpatchify_f32(dpatch, B, C, H, W, ps)
+            dx = ops.unpatchify_f32(gemm_dgrad_f32(B * T, K, D, gpatch, wb), B, C, H, W, ps)
         return dx, None, None, None, None, None
 
 
@@ -995,16 +1011,25 @@ class PatchEmbedFn(torch.autograd.Function):
 def _linear_wgrad(dy_bf, x_bf, w, rows):
     """w.grad [N, K] += dy^T x  (dy [rows, N], x [rows, K] with any row stride, both bf16)."""
     N, K = w.shape
-    ops.gemm(N, K, rows, dy_bf, N, x_bf, x_bf.stride(0), grad_buffer(w), K,
-             a_mode=L.OPND_MNMAJOR, b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
+    gemm_wgrad(N, K, rows, dy_bf, x_bf, grad_buffer(w))
 
 
-def _ln_fwd(x2d, norm, rows, D, out_bf):
-    mean = _empty((rows,), F32, x2d.device)
-    rstd = _empty((rows,), F32, x2d.device)
-    ops.layernorm_fwd(x2d, D, rows, D, norm.weight, norm.bias, norm.eps, out_bf, D, True, mean,
-                      rstd)
-    return mean, rstd
+def _ln_fwd(x2d, norm, rows, D, split=None, wide=None):
+    """A block's LayerNorm -> (bf16 rows, mean, rstd); with `split` (ops.layernorm_fwd_x3 /
+    ops.layernorm_fwd_h16) and wide = (columns, dtype) -> (the forward GEMM's operand, ...)."""
+    dev = x2d.device
+    if split is not None:
+        wide = _empty((rows, wide[0]), wide[1], dev)
+    tb = _empty((rows, D), BF16, dev)
+    mean = _empty((rows,), F32, dev)
+    rstd = _empty((rows,), F32, dev)
+    if split is None:
+        ops.layernorm_fwd(x2d, D, rows, D, norm.weight, norm.bias, norm.eps, tb, D, True, mean,
+                          rstd)
+    else:
+        split(x2d, D, rows, D, norm.weight, norm.bias, norm.eps, wide, tb, mean, rstd)
+        return wide, tb, mean, rstd
+    return tb, mean, rstd
 
 
 def _ln_bwd(dy_bf, x2d, mean, rstd, norm, rows, D, g, g_bf, gsum=False, batch=None):
@@ -1085,13 +1110,10 @@ class ViTBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, *params_and_mod):
         blk = params_and_mod[-1]
-        bm = blk._modules  # (nn.Module attributes are slow __getattr__ lookups)
-        attn, mlp = bm["attn"], bm["mlp"]
         B, T, D = x.shape
         rows = B * T
-        H = attn.num_heads
+        H = blk._modules["attn"].num_heads  # (nn.Module attributes are slow __getattr__ lookups)
         dh = D // H
-        dev = x.device
         x = x.detach().contiguous()
         x2 = x.view(rows, D)
         # the Linears' weights: the Function's own inputs (models.vit.Block._params order)
@@ -1102,15 +1124,23 @@ class ViTBlockFn(torch.autograd.Function):
         Dh = wfc1.shape[0]
         bias = lambda lin: lin.bias.detach() if lin.bias is not None else None  # noqa: E731
         mode = stage_mode(blk)
-        if mode == "bf16x3":
-            return ViTBlockFn._forward_x3(ctx, blk, x2, B, T, D, H, dh, rows, wqkv, wproj, wfc1,
-                                          wfc2, bias)
-        if mode == "fp16":
-            return ViTBlockFn._forward_h16(ctx, blk, x2, B, T, D, H, dh, rows, wqkv, wproj, wfc1,
-                                           wfc2, bias)
+        body = (ViTBlockFn._forward_x3 if mode == "bf16x3" else
+                ViTBlockFn._forward_h16 if mode == "fp16" else ViTBlockFn._forward_bf16)
+        xo, saved = body(blk, x2, B, T, D, H, dh, rows, wqkv, wproj, wfc1, wfc2, bias)
+        ctx.t768, ctx.blk, ctx.dims = _t768(), blk, (B, T, D, H, dh, Dh)
+        ctx.out_ref = weakref.ref(xo)
+        ctx.beside = _VIT_WGRAD_STREAM and _concurrent_encoders[0] == 0
+        ctx.save_for_backward(*saved, wqkv, wproj, wfc1, wfc2)
+        return xo
+
+    # The three bodies return (xo, (x2, xn1, m1, r1, qkv, o, lse, xm, xn2, m2, r2, dgl, h)).
+    @staticmethod
+    def _forward_bf16(blk, x2, B, T, D, H, dh, rows, wqkv, wproj, wfc1, wfc2, bias):
+        attn, mlp = blk.attn, blk.mlp
+        dev = x2.device
+        Dh = wfc1.shape[0]
         # attention branch
-        xn1 = _empty((rows, D), BF16, dev)
-        m1, r1 = _ln_fwd(x2, blk.norm1, rows, D, xn1)
+        xn1, m1, r1 = _ln_fwd(x2, blk.norm1, rows, D)
         qkv = _empty((rows, 3 * D), BF16, dev)
         ops.gemm(rows, 3 * D, D, xn1, D, wqkv, D, qkv, 3 * D, epilogue=L.EPI_BF16,
                  bias=bias(attn.qkv))
@@ -1120,8 +1150,7 @@ class ViTBlockFn(torch.autograd.Function):
         ops.gemm(rows, D, D, o, D, wproj, D, xm, D, epilogue=L.EPI_F32_RESID, bias=bias(attn.proj),
                  aux=x2, ldaux=D, tile=t768)
         # MLP branch
-        xn2 = _empty((rows, D), BF16, dev)
-        m2, r2 = _ln_fwd(xm, blk.norm2, rows, D, xn2)
+        xn2, m2, r2 = _ln_fwd(xm, blk.norm2, rows, D)
         dgl = _empty((rows, Dh), BF16, dev)
         h = _empty((rows, Dh), BF16, dev)
         ops.gemm(rows, Dh, D, xn2, D, wfc1, D, h, Dh, epilogue=L.EPI_BF16_GELU, bias=bias(mlp.fc1),
@@ -1129,40 +1158,22 @@ class ViTBlockFn(torch.autograd.Function):
         xo = _empty((B, T, D), F32, dev)
         ops.gemm(rows, D, Dh, h, Dh, wfc2, Dh, xo.view(rows, D), D, epilogue=L.EPI_F32_RESID,
                  bias=bias(mlp.fc2), aux=xm, ldaux=D, tile=t768)
-        ctx.t768 = t768
-        ctx.blk = blk
-        ctx.dims = (B, T, D, H, dh, Dh)
-        ctx.out_ref = weakref.ref(xo)
-        ctx.beside = _VIT_WGRAD_STREAM and _concurrent_encoders[0] == 0
-        ctx.save_for_backward(x2, xn1, m1, r1, qkv, o, lse, xm, xn2, m2, r2, dgl, h, wqkv,
-                              wproj, wfc1, wfc2)
-        return xo
+        return xo, (x2, xn1, m1, r1, qkv, o, lse, xm, xn2, m2, r2, dgl, h)
 
     @staticmethod
-    def _forward_x3(ctx, blk, x2, B, T, D, H, dh, rows, wqkv, wproj, wfc1, wfc2, bias):
+    def _forward_x3(blk, x2, B, T, D, H, dh, rows, wqkv, wproj, wfc1, wfc2, bias):
         """bf16x3 forward: the four Linears on split-bf16 triples (K tripled), fp32 GEMM
         outputs, fp32-accurate attention (split-bf16 MFMA); saves the same bf16 tensors as the
         bf16 forward."""
         attn, mlp = blk.attn, blk.mlp
         dev = x2.device
         Dh = wfc1.shape[0]
-
-        def ln_x3(xsrc, norm):
-            t3 = _empty((rows, 3 * D), BF16, dev)
-            tb = _empty((rows, D), BF16, dev)
-            mean = _empty((rows,), F32, dev)
-            rstd = _empty((rows,), F32, dev)
-            ops.layernorm_fwd_x3(xsrc, D, rows, D, norm.weight, norm.bias, norm.eps, t3, tb, mean,
-                                 rstd)
-            return t3, tb, mean, rstd
-
         tl = _X3_TILE
         # the two GEMMs to D = 768 columns (proj, fc2) on the 192 x 256 persistent tile when
         # the ViT runs alone (_t768: projx3 61.6-62.6 vs 71.1-71.2 us, fc2x3 250.8-251.0 vs
         # 270.9-271.9 us standalone; in the fusion step within noise of tile 8)
         tl_d = (_t768() or tl) if tl == 8 else tl
-        ctx.t768 = _t768()
-        xn1_3, xn1, m1, r1 = ln_x3(x2, blk.norm1)
+        xn1_3, xn1, m1, r1 = _ln_fwd(x2, blk.norm1, rows, D, ops.layernorm_fwd_x3, (3 * D, BF16))
         qkvf = _empty((rows, 3 * D), F32, dev)
         ops.gemm(rows, 3 * D, 3 * D, xn1_3, 3 * D, weight_x3_rows(attn.qkv.weight), 3 * D, qkvf,
                  3 * D, epilogue=L.EPI_F32, bias=bias(attn.qkv), tile=tl, x3=True)
@@ -1175,7 +1186,7 @@ class ViTBlockFn(torch.autograd.Function):
                  epilogue=L.EPI_F32_RESID, bias=bias(attn.proj), aux=x2, ldaux=D, tile=tl_d,
                  x3=True)
         del o3
-        xn2_3, xn2, m2, r2 = ln_x3(xm, blk.norm2)
+        xn2_3, xn2, m2, r2 = _ln_fwd(xm, blk.norm2, rows, D, ops.layernorm_fwd_x3, (3 * D, BF16))
         dgl = _empty((rows, Dh), BF16, dev)  # bf16 gelu'(pre): the DGELU factor
         if tl == 8:
             # fc1 + GELU with the split triple written by the epilogue; the backward's bf16 h
@@ -1196,16 +1207,10 @@ class ViTBlockFn(torch.autograd.Function):
         ops.gemm(rows, D, 3 * Dh, h3, 3 * Dh, weight_x3_rows(mlp.fc2.weight), 3 * Dh,
                  xo.view(rows, D), D, epilogue=L.EPI_F32_RESID, bias=bias(mlp.fc2), aux=xm,
                  ldaux=D, tile=tl_d, x3=True)
-        ctx.blk = blk
-        ctx.dims = (B, T, D, H, dh, Dh)
-        ctx.out_ref = weakref.ref(xo)
-        ctx.beside = _VIT_WGRAD_STREAM and _concurrent_encoders[0] == 0
-        ctx.save_for_backward(x2, xn1, m1, r1, qkv, o, lse, xm, xn2, m2, r2, dgl, h, wqkv,
-                              wproj, wfc1, wfc2)
-        return xo
+        return xo, (x2, xn1, m1, r1, qkv, o, lse, xm, xn2, m2, r2, dgl, h)
 
     @staticmethod
-    def _forward_h16(ctx, blk, x2, B, T, D, H, dh, rows, wqkv, wproj, wfc1, wfc2, bias):
+    def _forward_h16(blk, x2, B, T, D, H, dh, rows, wqkv, wproj, wfc1, wfc2, bias):
         """fp16 forward: the four Linears on fp16 operands (fp32 accumulate; persistent
         256 x 256 tile, 192 x 256 for the N = 768 GEMMs when the ViT runs alone), the fp16
         attention, fp32 residual stream; saves the same bf16 tensors as the bf16 forward (every
@@ -1216,20 +1221,9 @@ class ViTBlockFn(torch.autograd.Function):
         dev = x2.device
         Dh = wfc1.shape[0]
         F16 = torch.float16
-
-        def ln(xsrc, norm):
-            t16 = _empty((rows, D), F16, dev)
-            tb = _empty((rows, D), BF16, dev)
-            mean = _empty((rows,), F32, dev)
-            rstd = _empty((rows,), F32, dev)
-            ops.layernorm_fwd_h16(xsrc, D, rows, D, norm.weight, norm.bias, norm.eps, t16, tb,
-                                  mean, rstd)
-            return t16, tb, mean, rstd
-
         h16 = L.OPERAND_F16
-        ctx.t768 = _t768()
-        tl_d = ctx.t768 or 8
-        xn1_16, xn1, m1, r1 = ln(x2, bm["norm1"])
+        tl_d = _t768() or 8
+        xn1_16, xn1, m1, r1 = _ln_fwd(x2, bm["norm1"], rows, D, ops.layernorm_fwd_h16, (D, F16))
         # qkv in fp16 only: the attention backward rounds it to bf16 while staging
         # (same-box A/B: 21.56-21.62 vs 21.72-21.75 ms with the bf16 copy written too)
         qkv = _empty((rows, 3 * D), F16, dev)
@@ -1242,7 +1236,7 @@ class ViTBlockFn(torch.autograd.Function):
                  epilogue=L.EPI_F32_RESID, bias=bias(am["proj"]), aux=x2, ldaux=D, tile=tl_d,
                  operand_type=h16)
         del o16
-        xn2_16, xn2, m2, r2 = ln(xm, bm["norm2"])
+        xn2_16, xn2, m2, r2 = _ln_fwd(xm, bm["norm2"], rows, D, ops.layernorm_fwd_h16, (D, F16))
         # fc1 + GELU: [fp16 gelu | bf16 gelu] (fc2's operand, the backward's h) + bf16 gelu'
         h2 = _empty((rows, 2 * Dh), BF16, dev)
         dgl = _empty((rows, Dh), BF16, dev)
@@ -1255,13 +1249,7 @@ class ViTBlockFn(torch.autograd.Function):
         ops.gemm(rows, D, Dh, h2, 2 * Dh, weight_f16_rows(mm["fc2"].weight), Dh, xo.view(rows, D),
                  D, epilogue=L.EPI_F32_RESID, bias=bias(mm["fc2"]), aux=xm, ldaux=D, tile=tl_d,
                  operand_type=h16)
-        ctx.blk = blk
-        ctx.dims = (B, T, D, H, dh, Dh)
-        ctx.out_ref = weakref.ref(xo)
-        ctx.beside = _VIT_WGRAD_STREAM and _concurrent_encoders[0] == 0
-        ctx.save_for_backward(x2, xn1, m1, r1, qkv, o, lse, xm, xn2, m2, r2, dgl, h, wqkv,
-                              wproj, wfc1, wfc2)
-        return xo
+        return xo, (x2, xn1, m1, r1, qkv, o, lse, xm, xn2, m2, r2, dgl, h)
 
     @staticmethod
     def backward(ctx, gout):
@@ -1486,8 +1474,7 @@ class LinearFn(torch.autograd.Function):
                          epilogue=L.EPI_BF16 if out_bf else L.EPI_F32)
                 dx = dx.view(*ctx.lead, K)
             if wants(w):
-                ops.gemm(N, K, rows, gb, gb.shape[1], xs, K, grad_buffer(w), K,
-                         a_mode=L.OPND_MNMAJOR, b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
+                gemm_wgrad(N, K, rows, gb, xs, grad_buffer(w), ld_dy=gb.shape[1], ld_x=K)
         if wants(b):
             ops.colsum_add(g, grad_buffer(b))
         grads_done(w, b)

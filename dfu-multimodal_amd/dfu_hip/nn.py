@@ -12,7 +12,6 @@ import torch
 import torch.distributed as dist
 import torch.nn as tnn
 
-from . import _lib as L
 from . import functional as Fn
 from . import ops
 
@@ -27,60 +26,73 @@ class Conv2d(tnn.Conv2d):
     def forward(self, x):
         if self.bias is not None or self.groups != 1 or self.dilation != (1, 1):
             raise NotImplementedError("dfu_hip.nn.Conv2d: bias/groups/dilation unsupported")
-        C = x.shape[1]
+        if self.stride[0] != self.stride[1] or self.padding[0] != self.padding[1]:
+            raise NotImplementedError("dfu_hip.nn.Conv2d: square stride/padding only")
+        B, C, H, W = x.shape
         R, S = self.kernel_size
-        plain = R == 1 and S == 1 and self.stride == (1, 1) and self.padding == (0, 0)
-        if C % 64 != 0 and not plain:
+        g = ops.ConvGeom(B, H, W, C, self.out_channels, R, S, self.stride[0], self.padding[0])
+        if C % 64 != 0 and not g.plain:
             if Fn.krsc_strided(self.weight):
                 raise NotImplementedError(
                     "dfu_hip.nn.Conv2d: a channels-last (FusedAdamW) weight needs C % 64 == 0")
-            return Conv2dIm2colFn.apply(x, self.weight, self)
-        return Conv2dFn.apply(x, self.weight, self)
+            return Conv2dIm2colFn.apply(x, self.weight, self, g)
+        return Conv2dFn.apply(x, self.weight, self, g)
+
+
+class Conv2dFn(torch.autograd.Function):
+    """NHWC implicit GEMM (functional.conv_fwd / conv_dgrad / conv_wgrad); a geometry the
+    library does not take raises its DfuError.  Output and input gradient: bf16 channels_last."""
+
+    @staticmethod
+    def forward(ctx, x, w, mod, g):
+        xr = Fn.rows_view(Fn.nhwc_bf16(x.detach()))
+        wk = Fn.conv_weight_bf16(w)
+        M = g.n * g.p * g.q
+        y = torch.empty((M, g.k), dtype=torch.bfloat16, device=x.device)
+        # (conv_fwd's epilogue always emits the BN tile statistics: into a scratch slab here)
+        stats = torch.empty((ops.stats_tiles(M), 2, g.k), dtype=torch.float32, device=x.device)
+        Fn.conv_fwd(xr, g, wk, y, stats)
+        ctx.g, ctx.mod = g, mod
+        ctx.save_for_backward(xr, wk)
+        return Fn.from_rows(y, g.n, g.p, g.q, g.k)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xr, wk = ctx.saved_tensors
+        g, mod = ctx.g, ctx.mod
+        dy = Fn.rows_view(Fn.nhwc_bf16(gy))
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dxr = torch.empty((g.n * g.h * g.w, g.c), dtype=torch.bfloat16, device=xr.device)
+            Fn.conv_dgrad(dy, g, wk, dxr)
+            dx = Fn.from_rows(dxr, g.n, g.h, g.w, g.c)
+        Fn.conv_param_wgrad(mod, dy, xr, g)
+        return dx, None, None, None
 
 
 class Conv2dIm2colFn(torch.autograd.Function):
-    """Explicit im2col (bf16 [M][Kp], K = C*R*S padded to 16, (c, r, s) order as OIHW) + GEMM;
-    backward: weight gradient over the same columns, input gradient as fp32 dcol = dY W and its
-    col2im adjoint."""
+    """Explicit im2col + GEMM (functional.im2col_conv_*); backward: weight gradient over the
+    same rows, input gradient as fp32 dcol = dY W and its col2im adjoint."""
 
     @staticmethod
-    def forward(ctx, x, w, mod):
-        B, C, H, W = x.shape
-        R, S = mod.kernel_size
-        st, pad = mod.stride, mod.padding
-        if st[0] != st[1] or pad[0] != pad[1]:
-            raise NotImplementedError("dfu_hip.nn.Conv2d: square stride/padding only")
-        Kp = ((C * R * S + 15) // 16) * 16
-        xf = x.detach().float() if x.dtype != torch.float32 else x.detach()
-        col, P, Q = ops.im2col_f32(xf, R, S, st[0], pad[0], Kp)
-        wb = Fn.weight_bf16_rows(w, ld=Kp)
-        Cout, M = w.shape[0], B * P * Q
-        y = torch.empty((M, Cout), dtype=torch.bfloat16, device=x.device)
-        ops.gemm(M, Cout, Kp, col, Kp, wb, Kp, y, Cout, epilogue=L.EPI_BF16)
-        ctx.mod, ctx.dims, ctx.xdtype = mod, (B, C, H, W, P, Q, Kp, R, S, st[0], pad[0]), x.dtype
+    def forward(ctx, x, w, mod, g):
+        xf, wb = Fn.im2col_operands(x, w)
+        col, y, _ = Fn.im2col_conv_fwd(xf, wb, g, False)
+        ctx.mod, ctx.g, ctx.xdtype = mod, g, x.dtype
         ctx.save_for_backward(col, wb)
-        return Fn.from_rows(y, B, P, Q, Cout)
+        return Fn.from_rows(y, g.n, g.p, g.q, g.k)
 
     @staticmethod
     def backward(ctx, gy):
         col, wb = ctx.saved_tensors
-        B, C, H, W, P, Q, Kp, R, S, st, pad = ctx.dims
-        mod = ctx.mod
-        Cout, M, K = wb.shape[0], B * P * Q, C * R * S
         dy = Fn.rows_view(Fn.nhwc_bf16(gy))
-        if Fn.wants(mod.weight):
-            ops.gemm(Cout, K, M, dy, Cout, col, Kp, Fn.grad_buffer(mod.weight).view(Cout, K), K,
-                     a_mode=L.OPND_MNMAJOR, b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC)
-            Fn.grads_done(mod.weight)
+        Fn.im2col_conv_wgrad(dy, col, ctx.mod.weight, ctx.g)
         dx = None
         if ctx.needs_input_grad[0]:
-            dcol = torch.empty((M, Kp), dtype=torch.float32, device=dy.device)
-            ops.gemm(M, Kp, Cout, dy, Cout, wb, Kp, dcol, Kp, b_mode=L.OPND_MNMAJOR,
-                     epilogue=L.EPI_F32)
-            dx = ops.col2im_f32(dcol, B, C, H, W, R, S, st, pad, P, Q, Kp)
+            dx = Fn.im2col_conv_dx(dy, wb, ctx.g)
             if ctx.xdtype != torch.float32:
                 dx = dx.to(ctx.xdtype)
-        return dx, None, None
+        return dx, None, None, None
 
 
 class BatchNorm2d(tnn.BatchNorm2d):

@@ -39,13 +39,14 @@ def _req(t, dtype, name):
 class ConvGeom:
     """Implicit-GEMM convolution geometry (NHWC input N,H,W,C; K filters of R x S)."""
 
-    __slots__ = ("n", "h", "w", "c", "k", "r", "s", "stride", "pad", "p", "q")
+    __slots__ = ("n", "h", "w", "c", "k", "r", "s", "stride", "pad", "p", "q", "plain")
 
     def __init__(self, n, h, w, c, k, r, s, stride, pad):
         self.n, self.h, self.w, self.c, self.k = n, h, w, c, k
         self.r, self.s, self.stride, self.pad = r, s, stride, pad
         self.p = (h + 2 * pad - r) // stride + 1
         self.q = (w + 2 * pad - s) // stride + 1
+        self.plain = r == 1 and s == 1 and stride == 1 and pad == 0  # a GEMM over the rows
 
 
 TILES = {"auto": 0, "128x128": 1, "256x128": 2, "128x256": 3, "256x256": 4, "128x128o2": 5,

@@ -82,6 +82,49 @@ def test_conv2d_standalone_any_channel_count(C, K, R, stride, pad):
     assert rel(conv.weight.grad, ref.weight.grad) < 1e-2, rel(conv.weight.grad, ref.weight.grad)
 
 
+def _check_conv2d_implicit(C, K, R, stride, pad, fused_adamw=False):
+    from dfu_hip import functional as Fn
+    from dfu_hip import nn as hnn
+    torch.manual_seed(2)
+    conv = hnn.Conv2d(C, K, R, stride=stride, padding=pad, bias=False).to(DEV)
+    if fused_adamw:  # the weight moves to channels-last storage with a bf16 shadow
+        from dfu_hip.optim import FusedAdamW
+        FusedAdamW(conv.parameters())
+        assert Fn.krsc_strided(conv.weight) and Fn.krsc_strided(conv.weight.grad)
+    ref = torch.nn.Conv2d(C, K, R, stride=stride, padding=pad, bias=False).to(DEV)
+    with torch.no_grad():
+        ref.weight.copy_(_bf(conv.weight))
+    x = torch.randn(2, C, 9, 7, device=DEV).requires_grad_(True)  # M = 126 at stride 1
+    xr = _bf(x.detach()).requires_grad_(True)
+    y = conv(x)
+    yr = ref(xr)
+    assert y.shape == yr.shape and y.dtype == torch.bfloat16
+    assert rel(y, yr) < 1e-2, rel(y, yr)
+    g = torch.randn(y.shape, device=DEV)
+    grad_before = conv.weight.grad
+    (y.float() * g).sum().backward()
+    (yr * _bf(g)).sum().backward()
+    assert x.grad.shape == x.shape
+    assert rel(x.grad, xr.grad) < 1e-2, rel(x.grad, xr.grad)
+    assert rel(conv.weight.grad, ref.weight.grad) < 1e-2, rel(conv.weight.grad, ref.weight.grad)
+    if fused_adamw:  # accumulated in place, into the optimizer's flat buffer
+        assert conv.weight.grad is grad_before
+
+
+@pytest.mark.parametrize("C,K,R,stride,pad", [(64, 64, 3, 1, 1), (64, 64, 3, 2, 1),
+                                               (32, 64, 1, 1, 0)])
+def test_conv2d_standalone_implicit_gemm(C, K, R, stride, pad):
+    """Input channels a multiple of 64, or a plain 1x1: the NHWC implicit GEMM (Conv2dFn), with
+    a ragged 128-row tile (M = 126) and, at stride 2, the phase-split input gradient."""
+    _check_conv2d_implicit(C, K, R, stride, pad)
+
+
+def test_conv2d_standalone_implicit_gemm_fused_adamw_weight():
+    """Under FusedAdamW the 3x3 weight is stored channels-last: the forward reads its bf16
+    shadow as the operand and the weight gradient accumulates straight into p.grad."""
+    _check_conv2d_implicit(64, 64, 3, 1, 1, fused_adamw=True)
+
+
 def test_conv2d_channels_last_weight_needs_c64():
     """A FusedAdamW-managed spatial weight is stored KRSC; the explicit (c, r, s) im2col cannot
     read it, so a channel count the implicit GEMM cannot take raises a clear error."""
