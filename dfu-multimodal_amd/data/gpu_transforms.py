@@ -40,14 +40,11 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 THERMAL_MEAN = (0.5, 0.5, 0.5)
 THERMAL_STD = (0.5, 0.5, 0.5)
 
-BRIGHTNESS, CONTRAST, SATURATION = 0, 1, 2  # enum dfu_aug_op
+BRIGHTNESS, CONTRAST, SATURATION = (L.DFU_AUG_BRIGHTNESS, L.DFU_AUG_CONTRAST,
+                                    L.DFU_AUG_SATURATION)  # enum dfu_aug_op
 
-RESIZE_DESC = np.dtype([("src_off", "<i8"), ("tmp_off", "<i8"), ("coef_off", "<i8"),
-                        ("w", "<i4"), ("h", "<i4"), ("ksh", "<i4"), ("ksv", "<i4")])
-AUG_PARAMS = np.dtype([("hflip", "<i4"), ("vflip", "<i4"), ("rotate", "<i4"), ("rot", "<i4", 6),
-                       ("affine", "<i4"), ("aff", "<i4", 6), ("n_ops", "<i4"), ("op", "<i4", 3),
-                       ("factor", "<f4", 3)])
-assert RESIZE_DESC.itemsize == 40 and AUG_PARAMS.itemsize == 92  # the C structs
+RESIZE_DESC = np.dtype(L.ResizeDesc)  # dfu_resize_desc
+AUG_PARAMS = np.dtype(L.AugParams)    # dfu_aug_params
 
 
 @dataclass(frozen=True)
@@ -89,7 +86,8 @@ rgb_tta_transform = TransformSpec(hflip_p=0.5, vflip_p=0.5, rotation=15,
 thermal_tta_transform = TransformSpec(hflip_p=0.5, vflip_p=0.5, rotation=15,
                                       affine=(10, (0.05, 0.05), None), affine_p=None,
                                       mean=THERMAL_MEAN, std=THERMAL_STD, order="rotate_flip")
-ORDERS = {"flip_rotate": 0, "rotate_flip": 1}  # enum dfu_aug_order
+ORDERS = {"flip_rotate": L.DFU_AUG_ORDER_FLIP_ROTATE,
+          "rotate_flip": L.DFU_AUG_ORDER_ROTATE_FLIP}  # enum dfu_aug_order
 
 
 @dataclass

@@ -2,6 +2,12 @@
 
 This is the only place the host touches the native library.  Loading fails loudly: there is
 no CPU or ATen fallback for any op on the hot path (SURVEY.md §7 design stance).
+
+Nothing of the ABI is written out here.  The header is read once at import by parse_header, a
+strict reader of the restricted grammar the header uses (not a C parser): prototypes, `typedef
+struct`s of scalars, pointers and scalar arrays, enums whose enumerators all carry `= n`, and
+integer `#define`s.  Text it does not recognise raises HeaderError; it never guesses or skips.
+The GEMM tile ids come the same way from the DFU_TILES rows of csrc/gemm_table.h (parse_tiles).
 """
 import ctypes
 import os
@@ -11,185 +17,156 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # DFU_HIP_LIB: another build of the library (A/B timing of two builds); default: in-tree
 LIB_PATH = os.environ.get("DFU_HIP_LIB") or os.path.join(_HERE, "libdfu_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "dfu_hip.h"))
+TILE_TABLE_PATH = os.path.normpath(os.path.join(_HERE, "..", "csrc", "gemm_table.h"))
 
-c_int32 = ctypes.c_int32
-c_int64 = ctypes.c_int64
 c_float = ctypes.c_float
-c_uint64 = ctypes.c_uint64
 c_void_p = ctypes.c_void_p
-c_char_p = ctypes.c_char_p
 
-# enum dfu_operand_mode
-OPND_KMAJOR, OPND_MNMAJOR, OPND_CONV_FWD, OPND_CONV_DGRAD, OPND_CONV_DGRAD_W, OPND_CONV_WGRAD_X = range(6)
-# enum dfu_epilogue
-(EPI_BF16, EPI_BF16_RELU, EPI_BF16_GELU, EPI_F32, EPI_F32_RESID, EPI_BF16_DGELU, EPI_BF16_ADD,
- EPI_F32_ACC, EPI_F32_ACC_CONVW, EPI_BF16_STATS, EPI_PATCH, EPI_F32_STATS,
- EPI_BF16_DSTATS, EPI_X3_GELU, EPI_F16_DUAL, EPI_F16_GELU) = range(16)
-# dfu_gemm_desc.operand_type
-OPERAND_BF16, OPERAND_F16 = 0, 1
+_SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+            "float": c_float}
+_POINTEES = set(_SCALARS) | {"void", "double", "uint8_t"}  # and every struct declared so far
+_RETURNS = {"int": ctypes.c_int32, "int64_t": ctypes.c_int64, "const char *": ctypes.c_char_p}
 
-DFU_E_INVALID = 1001
-DFU_E_UNSUPPORTED = 1002
-
-
-class GemmDesc(ctypes.Structure):
-    """Mirror of `dfu_gemm_desc` (include/dfu_hip.h)."""
-    _fields_ = [
-        ("M", c_int32), ("N", c_int32), ("K", c_int32),
-        ("a_mode", c_int32), ("b_mode", c_int32),
-        ("A", c_void_p), ("lda", c_int64),
-        ("B", c_void_p), ("ldb", c_int64),
-        ("C", c_void_p), ("ldc", c_int64),
-        ("epilogue", c_int32), ("alpha", c_float),
-        ("bias", c_void_p),
-        ("aux", c_void_p), ("ldaux", c_int64),
-        ("aux_out", c_void_p), ("ldaux_out", c_int64),
-        ("stats", c_void_p),
-        ("split_k", c_int32),
-        ("ep_tokens", c_int32),
-        ("conv_n", c_int32), ("conv_h", c_int32), ("conv_w", c_int32), ("conv_c", c_int32),
-        ("conv_k", c_int32), ("conv_r", c_int32), ("conv_s", c_int32),
-        ("conv_stride", c_int32), ("conv_pad", c_int32),
-        ("conv_p", c_int32), ("conv_q", c_int32),
-        ("tile", c_int32),
-        ("workspace", c_void_p), ("workspace_bytes", c_int64),
-        ("tile_counters", c_void_p), ("tile_counters_len", c_int32),
-        ("operand_type", c_int32),
-        ("a_seg", c_int32), ("a_lo", c_void_p),
-        ("x3_pairs", c_int32),
-    ]
+_COMMENT = re.compile(r"/\*.*?\*/|//[^\n]*", re.S)
+_PREPROCESSOR = re.compile(r"#\s*(ifndef\s+\w+_H|define\s+\w+_H|include\s+<stdint\.h>)")
+_DEFINE = re.compile(r"#\s*define\s+(\w+)\s+(\S+)")
+_DECLARATION = re.compile(
+    r"\s*(?:enum\s+(\w+)\s*\{([^{}]*)\}"
+    r"|typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)"
+    r"|(const\s+char\s*\*|\w+)\s+(\w+)\s*\(([^()]*)\))\s*;")
+# `[const] T name`, `[const] T* name`, `T* const* name`: base type, pointer part, the rest
+_TYPED = re.compile(r"(?:const\s+)?(\w+)(\s+|\s*(?:\*\s*(?:const\b\s*)?)+)(.+)", re.S)
+_DECLARATOR = re.compile(r"(\w+)(?:\s*\[\s*(\d+)\s*\])?")
 
 
-class ReduceEntry(ctypes.Structure):
-    """Mirror of `dfu_reduce_entry` (include/dfu_hip.h)."""
-    _fields_ = [("partial", c_void_p), ("stride", c_int64), ("out", c_void_p),
-                ("blocks", c_int32), ("D", c_int32)]
+class HeaderError(ValueError):
+    """include/dfu_hip.h (or the tile table) holds text the reader does not recognise."""
 
 
-REDUCE_BATCH = 8
-P = c_void_p
-I32 = c_int32
-I64 = c_int64
-F = c_float
-
-# name -> argtypes (restype is always int32 unless listed in _RESTYPE)
-PROTOTYPES = {
-    "dfu_last_error_string": [],
-    "dfu_version": [],
-    "dfu_zero": [P, I64, P],
-    "dfu_streams_abort_capture": [P, I32, P],
-    "dfu_stream_capture_status": [P, P],
-    "dfu_stream_create": [I32, P],
-    "dfu_stream_destroy": [P],
-    "dfu_stream_wait": [P, P],
-    "dfu_gemm": [ctypes.POINTER(GemmDesc), P],
-    "dfu_gemm_stats_tiles": [I32],
-    "dfu_gemm_workspace_bytes": [ctypes.POINTER(GemmDesc)],
-    "dfu_gemm_plan": [ctypes.POINTER(GemmDesc), ctypes.POINTER(c_int32), ctypes.POINTER(c_int32)],
-    "dfu_gemm_set_persistent": [I32],
-    "dfu_gemm_set_inkernel_reduce": [I32],
-    "dfu_gemm_set_tail_split": [I32],
-    "dfu_gemm_f32": [I32, I32, I32, P, I64, I64, P, I64, I64, P, I64, P, I32, I32, P, I64, P],
-    "dfu_gemm_f32_workspace_bytes": [I32, I32, I32],
-    "dfu_pack_conv_weight": [P, P, I32, I32, I32, I32, P],
-    "dfu_conv_grad_krsc_to_oihw": [P, P, I32, I32, I32, I32, P],
-    "dfu_cast_rows_bf16": [P, I64, P, I64, I32, I32, P],
-    "dfu_transpose_bf16": [P, I32, I32, P],
-    "dfu_cast_rows_f32": [P, I64, P, I64, I32, I32, P],
-    "dfu_cast_rows_f16": [P, I64, P, I64, I32, I32, P],
-    "dfu_im2col_f32": [P, I64, I64, I64, I64, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, I32, P],
-    "dfu_patchify_f32": [P, I64, I64, I64, I64, I32, I32, I32, I32, I32, P, P],
-    "dfu_col2im_f32": [P, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, P],
-    "dfu_unpatchify_f32": [P, I32, I32, I32, I32, I32, P, P],
-    "dfu_gradcam": [P, I32, I64, I64, I64, P, I32, I64, I64, I64, I32, I32, I32, P, P],
-    "dfu_saliency": [P, I32, I32, I32, P, P],
-    "dfu_bn_finalize": [P, I32, I32, I32, P, P, F, F, P, P, P, P, P, P, P, P, P, I32, P],
-    "dfu_bn_finalize_ws_bytes": [I32, I32],
-    "dfu_bn_bwd_finalize_ws_bytes": [I32, I32],
-    "dfu_bn_eval_coeffs": [P, P, P, P, F, I32, P, P, P],
-    "dfu_bn_apply": [P, P, P, P, I32, P, I64, I32, P],
-    "dfu_bn_tile_stats": [P, I64, I32, P, P],
-    "dfu_bn_apply_mask": [P, P, P, P, I32, P, P, I64, I32, P],
-    "dfu_bn_bwd_blocks": [I64, I32],
-    "dfu_bn_bwd_reduce": [P, P, P, I32, P, P, P, P, I64, I32, P, P],
-    "dfu_bn_bwd_finalize": [P, I32, I64, I32, P, P, I32, P, P, P, P, P, I32, P],
-    "dfu_bn_bwd_apply": [P, P, P, I32, P, P, P, P, P, I64, I32, P, P, P],
-    "dfu_bn_bwd_ws_bytes": [I64, I32],
-    "dfu_bn_bwd": [P, P, P, I32, P, P, P, P, P, I64, I32, I32, P, P, P, P, P, I64, P, I32, P],
-    "dfu_maxpool_fwd": [P, I32, I32, I32, I32, P, P, I32, I32, P],
-    "dfu_maxpool_bn_fwd": [P, P, P, I32, I32, I32, I32, P, P, I32, I32, P],
-    "dfu_maxpool_bwd": [P, P, I32, I32, I32, I32, I32, I32, P, P],
-    "dfu_avgpool_fwd": [P, I32, I32, I32, P, P],
-    "dfu_avgpool_bwd": [P, I32, I32, I32, P, P],
-    "dfu_layernorm_fwd": [P, I64, I32, I32, P, P, F, P, I64, I32, P, P, P],
-    "dfu_ln_bwd_blocks": [I32],
-    "dfu_layernorm_bwd": [P, I64, I32, P, I64, P, P, P, I32, I32, P, I64, P, P, P, P],
-    "dfu_reduce_partials": [P, I32, I32, I32, P, P, P],
-    "dfu_reduce_partials_batch": [ctypes.POINTER(ReduceEntry), I32, P],
-    "dfu_attention_fwd": [P, I32, I32, I32, I32, F, P, P, P],
-    "dfu_attention_fwd_f16": [P, I32, I32, I32, I32, F, P, P, P, P],
-    "dfu_attention_bwd": [P, P, P, P, I32, I32, I32, I32, F, P, P, P],
-    "dfu_attention_bwd_qkv16": [P, P, P, P, I32, I32, I32, I32, F, P, P, P],
-    "dfu_attention_npad": [I32],
-    "dfu_vit_cls_rows": [P, P, P, I32, I32, I32, P],
-    "dfu_vit_embed_bwd": [P, I32, I32, I32, P, P, P, P, P, P],
-    "dfu_colsum": [P, I32, I64, I32, I32, P, P, P],
-    "dfu_colsum_blocks": [I32],
-    "dfu_gather_rows_f32": [P, I64, I32, I32, I32, I32, P, I64, P],
-    "dfu_scatter_rows_f32": [P, I64, I32, I32, I32, I32, P, I64, P],
-    "dfu_relu_fwd": [P, P, I64, I32, P],
-    "dfu_relu_bwd": [P, P, P, I64, I32, P],
-    "dfu_dropout_fwd": [P, P, P, I64, F, c_uint64, P, I32, P],
-    "dfu_dropout_bwd": [P, P, P, I64, F, I32, P],
-    "dfu_concat2_bf16": [P, I32, I32, P, I32, I32, I32, P, P],
-    "dfu_split2_f32": [P, I32, I32, I32, I32, P, P, P],
-    "dfu_ce_weighted_fwd": [P, P, P, I32, I32, P, P, P],
-    "dfu_ce_weighted_bwd": [P, P, I32, I32, P, P],
-    "dfu_adamw": [P, P, P, P, P, I32, P, I32, F, F, F, F, F, P, P],
-    "dfu_adamw_flat": [P, P, P, P, I64, F, F, F, F, F, P, P, P, P, I64, I64, P],
-    "dfu_step_increment": [P, P],
-    "dfu_argmax_rows": [P, I32, I32, P, P],
-    "dfu_softmax_rows": [P, I32, I32, P, P],
-    "dfu_metrics_accumulate": [P, P, I32, I32, P, P, P, P, P],
-    "dfu_split_x3": [P, I64, I32, I32, I32, P, I32, P, I64, P],
-    "dfu_pack_conv_weight_x3": [P, P, I32, I32, I32, I32, I32, P],
-    "dfu_stem_conv_x3": [P, I64, I64, I64, I64, I32, I32, I32, I32, P, I32, I32, I32, I32, I32,
-                         P, P, P, P, P],
-    "dfu_stem_wgrad_ws_bytes": [I32, I32, I32],
-    "dfu_stem_wgrad_x3": [P, I64, I64, I64, I64, I32, I32, I32, I32, P, I32, I32, I32, I32, I32,
-                          P, P, I64, P],
-    "dfu_maxpool_bn_fwd_x3": [P, P, P, P, I32, I32, I32, I32, P, P, P, P, I32, I32, P],
-    "dfu_im2col_f32_x3": [P, I64, I64, I64, I64, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, P, I32, P],
-    "dfu_patchify_f32_x3": [P, I64, I64, I64, I64, I32, I32, I32, I32, I32, P, P],
-    "dfu_bn_apply_x3": [P, P, P, P, P, P, I32, I32, P, P, P, P, P, I64, I32, P],
-    "dfu_maxpool_fwd_x3": [P, I32, I32, I32, I32, P, P, P, I32, I32, P],
-    "dfu_avgpool_fwd_x3": [P, P, I32, I32, I32, P, P],
-    "dfu_layernorm_fwd_x3": [P, I64, I32, I32, P, P, F, P, P, P, P, P],
-    "dfu_layernorm_fwd_h16": [P, I64, I32, I32, P, P, F, P, P, P, P, P],
-    "dfu_gelu_x3": [P, I64, I32, P, P, P, P],
-    "dfu_attention_fwd_f32": [P, I32, I32, I32, I32, F, I32, P, P, P, P, P],
-    "dfu_resize_ksize": [I32, I32],
-    "dfu_resize_coeffs": [I32, I32, P, P],
-    "dfu_resize_batch": [P, P, P, I32, I32, I32, P, P, P],
-    "dfu_augment_normalize": [P, P, I32, I32, I32, P, P, P, P, P],
-    "dfu_augment_views": [P, I32, P, P, I32, I32, I32, I32, P, P, P, P, P],
-    "dfu_tta_reduce": [P, I32, I32, I32, P, P, P],
-    "dfu_binary_eval_counts": [P, P, P, I32, P, P],
-    "dfu_binary_curve": [P, P, I32, P, P, P, P, P, P],
-    "dfu_image_minmax": [P, I32, I32, P, P],
-    "dfu_cam_overlay": [P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P, P, F, P, P, P, P],
-}
-_RESTYPE = {"dfu_last_error_string": c_char_p, "dfu_gemm_workspace_bytes": c_int64,
-            "dfu_gemm_f32_workspace_bytes": c_int64, "dfu_bn_finalize_ws_bytes": c_int64,
-            "dfu_bn_bwd_finalize_ws_bytes": c_int64, "dfu_stem_wgrad_ws_bytes": c_int64,
-            "dfu_bn_bwd_ws_bytes": c_int64}
+def _integer(text, where):
+    try:
+        return int(text, 0)
+    except ValueError:
+        raise HeaderError(f"not an integer constant: {where.strip()!r}") from None
 
 
-def header_symbols(path=HEADER_PATH):
-    """Every function name declared in include/dfu_hip.h (used by the symbol-export test)."""
-    with open(path) as f:
-        text = f.read()
-    return sorted(set(re.findall(r"^\s*(?:int|int64_t|const char\*)\s+(dfu_\w+)\s*\(", text, re.M)))
+def _typed(text, structs):
+    """`[const] T [*...] rest` -> (ctypes type, rest); any pointer is a c_void_p."""
+    m = _TYPED.fullmatch(text.strip())
+    if not m:
+        raise HeaderError(f"unrecognised parameter or field: {text.strip()!r}")
+    base, pointer = m[1], "*" in m[2]
+    if base not in (_POINTEES | set(structs) if pointer else _SCALARS):
+        raise HeaderError(f"unknown type {base!r} in {text.strip()!r}")
+    return (c_void_p if pointer else _SCALARS[base]), m[3]
+
+
+def _struct(name, body, structs):
+    fields = []
+    *stmts, tail = body.split(";")
+    for stmt in stmts:
+        ctype, rest = _typed(stmt, structs)
+        declarators = [_DECLARATOR.fullmatch(d.strip()) for d in rest.split(",")]
+        if not all(declarators) or (ctype is c_void_p and len(declarators) > 1):
+            raise HeaderError(f"unrecognised field in struct {name}: {stmt.strip()!r}")
+        fields += [(d[1], ctype * int(d[2]) if d[2] else ctype) for d in declarators]
+    if tail.strip() or not fields:
+        raise HeaderError(f"unrecognised text in struct {name}: {tail.strip()!r}")
+    return type(name, (ctypes.Structure,), {"_fields_": fields,
+                                            "__doc__": f"`{name}` of include/dfu_hip.h."})
+
+
+def _function(ret, params, structs):
+    ret = " ".join(ret.replace("*", " *").split())
+    if ret not in _RETURNS:
+        raise HeaderError(f"unknown return type {ret!r}")
+    argtypes = []
+    if params.strip() != "void":
+        for p in params.split(","):
+            ctype, name = _typed(p, structs)
+            if not re.fullmatch(r"\w+", name):
+                raise HeaderError(f"unrecognised parameter: {p.strip()!r}")
+            argtypes.append(ctype)
+    return _RETURNS[ret], argtypes
+
+
+def parse_header(text):
+    """The header's text -> (functions: name -> (restype, argtypes), structs: name ->
+    ctypes.Structure class, enums: name -> {enumerator: value}, constants: #define -> value)."""
+    functions, structs, enums, constants = {}, {}, {}, {}
+    lines, cplusplus = [], False
+    for line in _COMMENT.sub(" ", text).splitlines():
+        s = line.strip()
+        if not s.startswith("#"):
+            if not cplusplus:  # `extern "C" {` and its `}`: not part of the C view
+                lines.append(line)
+        elif s == "#ifdef __cplusplus":
+            cplusplus = True
+        elif s == "#endif":
+            cplusplus = False
+        elif m := _DEFINE.fullmatch(s):
+            constants[m[1]] = _integer(m[2], s)
+        elif not _PREPROCESSOR.fullmatch(s):
+            raise HeaderError(f"unrecognised preprocessor line: {s!r}")
+    src, pos = "\n".join(lines), 0
+    while src[pos:].strip():
+        m = _DECLARATION.match(src, pos)
+        if not m:
+            raise HeaderError(f"unrecognised declaration: {src[pos:].split(';')[0].strip()!r}")
+        pos = m.end()
+        if m[1]:
+            enums[m[1]] = {}
+            for item in m[2].split(","):
+                e = re.fullmatch(r"\s*(\w+)\s*=\s*(\S+)\s*", item)
+                if not e:
+                    raise HeaderError(f"enum {m[1]}: enumerator without `= n`: {item.strip()!r}")
+                enums[m[1]][e[1]] = _integer(e[2], item)
+        elif m[3]:
+            if m[3] != m[5]:
+                raise HeaderError(f"typedef struct {m[3]} is named {m[5]}")
+            structs[m[3]] = _struct(m[3], m[4], structs)
+        else:
+            functions[m[7]] = _function(m[6], m[8], structs)
+    return functions, structs, enums, constants
+
+
+def parse_tiles(text):
+    """csrc/gemm_table.h -> [(name, TM, TN, phased)], the DFU_TILES rows: tile id = row + 1."""
+    m = re.search(r"^#define DFU_TILES\(X\)((?:.*\\\n)*.*)", _COMMENT.sub(" ", text), re.M)
+    if not m:
+        raise HeaderError("no DFU_TILES table")
+    rows = []
+    for line in m[1].replace("\\\n", "\n").split("\n"):
+        r = re.fullmatch(r"X\((\w+), (\d+), (\d+), \d+, (true|false), (?:true|false), [\d.]+, "
+                         r"[\d.]+\)", line.strip())
+        if r:
+            rows.append((r[1], int(r[2]), int(r[3]), r[4] == "true"))
+        elif line.strip():
+            raise HeaderError(f"unrecognised DFU_TILES row: {line.strip()!r}")
+    return rows
+
+
+with open(HEADER_PATH) as _f:
+    FUNCTIONS, STRUCTS, ENUMS, CONSTANTS = parse_header(_f.read())
+with open(TILE_TABLE_PATH) as _f:
+    TILE_ROWS = parse_tiles(_f.read())
+
+GemmDesc = STRUCTS["dfu_gemm_desc"]
+ReduceEntry = STRUCTS["dfu_reduce_entry"]
+TransposeJob = STRUCTS["dfu_transpose_job"]
+ResizeDesc = STRUCTS["dfu_resize_desc"]
+AugParams = STRUCTS["dfu_aug_params"]
+
+# Every enumerator and #define, by its header name (DFU_E_INVALID, DFU_AUG_CONTRAST) and by that
+# name without the DFU_ (OPND_KMAJOR, EPI_F32_ACC, OPERAND_F16, X3_PAIRS, REDUCE_BATCH).
+for _values in (CONSTANTS, *ENUMS.values()):
+    globals().update(_values)
+    globals().update({k.removeprefix("DFU_"): v for k, v in _values.items()})
+
+
+def header_symbols():
+    """Every function name declared in include/dfu_hip.h."""
+    return sorted(FUNCTIONS)
 
 
 class DfuError(RuntimeError):
@@ -211,10 +188,10 @@ def load():
             f"libdfu_hip.so not found at {LIB_PATH}; build it with "
             f"`make -C dfu-multimodal_amd` (or __graft_entry__.build()). There is no fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in PROTOTYPES.items():
+    for name, (restype, argtypes) in FUNCTIONS.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
-        fn.restype = _RESTYPE.get(name, c_int32)
+        fn.restype = restype
     _lib = lib
     return lib
 

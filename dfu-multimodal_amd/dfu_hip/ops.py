@@ -49,9 +49,10 @@ class ConvGeom:
         self.plain = r == 1 and s == 1 and stride == 1 and pad == 0  # a GEMM over the rows
 
 
-TILES = {"auto": 0, "128x128": 1, "256x128": 2, "128x256": 3, "256x256": 4, "128x128o2": 5,
-         "128x128w4": 6, "256x256p8": 7, "256x256ps": 8, "192x256ps": 9, "256x64": 10,
-         "128x64o2": 11}
+# dfu_gemm_desc.tile: name -> id and id -> (TM, TN, phased), the DFU_TILES rows of
+# csrc/gemm_table.h (id = row + 1)
+TILES = {"auto": 0, **{row[0]: i for i, row in enumerate(L.TILE_ROWS, 1)}}
+TILE_DIMS = {i: row[1:] for i, row in enumerate(L.TILE_ROWS, 1)}
 
 # Optional recording of GEMM launches (bench.py's roofline): when set to a list, every
 # dfu_gemm call appends (descriptor, algorithmic flops, tensors it touches) — the tensor
@@ -263,9 +264,8 @@ class TransposeJobs:
     sizes multiples of 8, 16-B aligned)."""
 
     def __init__(self, pairs):
-        import struct
-        raw, tile0 = bytearray(), 0
-        for src, dst in pairs:
+        jobs, tile0 = (L.TransposeJob * len(pairs))(), 0
+        for job, (src, dst) in zip(jobs, pairs):
             _req(src, BF16, "transpose_bf16")
             _req(dst, BF16, "transpose_bf16")
             r, c = src.shape
@@ -275,13 +275,14 @@ class TransposeJobs:
             if not ok:
                 raise ValueError(f"transpose_bf16: [{r}, {c}] stride {src.stride()} -> "
                                  f"{tuple(dst.shape)} stride {dst.stride()} unsupported")
-            raw += struct.pack("<QQiiiiii", src.data_ptr(), dst.data_ptr(), r, c, tile0,
-                               src.stride(0), dst.stride(0), 0)
+            job.src, job.dst = src.data_ptr(), dst.data_ptr()
+            job.rows, job.cols, job.tile0 = r, c, tile0
+            job.ld_src, job.ld_dst = src.stride(0), dst.stride(0)
             tile0 += ((r + 63) // 64) * ((c + 63) // 64)
         self.pairs = list(pairs)  # keep the buffers alive as long as the table
         self.njobs, self.ntiles = len(self.pairs), tile0
         dev = self.pairs[0][0].device
-        self.table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
+        self.table = torch.frombuffer(bytearray(jobs), dtype=torch.uint8).to(dev)
 
     def launch(self):
         check(lib().dfu_transpose_bf16(ptr(self.table), self.njobs, self.ntiles, stream_ptr()),
@@ -743,8 +744,9 @@ def softmax_rows(x):
 # --------------------------------------------------------------- bf16x3 (split) forward
 # csrc/precise.hip: a triple is bf16 [rows][3C] = [hi | lo | hi] (pattern 0, GEMM A operand)
 # or [hi | hi | lo] (pattern 1, GEMM B operand / weights), hi = bf16(x), lo = bf16(x - hi).
-X3_A, X3_B = 0, 1
-X3_PAIRS = 2  # B operand of dfu_gemm_desc.x3_pairs: [rows][2 seg], per 32 columns [hi | lo]
+# enum dfu_x3_pattern; X3_PAIRS: the B operand of dfu_gemm_desc.x3_pairs, [rows][2 seg], per 32
+# columns [hi | lo]
+X3_A, X3_B, X3_PAIRS = L.X3_A, L.X3_B, L.X3_PAIRS
 
 
 def split_x3(x, pattern, seg=None, hi_out=None):

@@ -98,6 +98,8 @@ enum dfu_epilogue {
                                 fc2's fp16 operand at column 0, the backward's bf16 h at
                                 column N), aux_out bf16 = gelu'(pre).  operand_type 1 only.  */
 };
+/* dfu_gemm_desc.operand_type: the element type of A and B */
+enum dfu_operand_type { DFU_OPERAND_BF16 = 0, DFU_OPERAND_F16 = 1 };
 
 typedef struct dfu_gemm_desc {
   int32_t M, N, K;
@@ -499,6 +501,9 @@ int dfu_metrics_accumulate(const float* logits, const int64_t* labels, int32_t r
  * hi = bf16(x), lo = bf16(x - hi); a triple is bf16 [rows][3C].  GEMM outputs stay fp32
  * (DFU_EPI_F32 / F32_RESID / F32_STATS / PATCH); the kernels below also write the plain bf16
  * tensors the (bf16) backward pass saves.  Reference ops: the same as their bf16 twins above. */
+/* The `pattern` of dfu_split_x3 and dfu_pack_conv_weight_x3: the A triple, the B triple, or
+ * the interleaved pairs of dfu_gemm_desc.x3_pairs. */
+enum dfu_x3_pattern { DFU_X3_A = 0, DFU_X3_B = 1, DFU_X3_PAIRS = 2 };
 /* fp32 [rows][cols] (ld_in) -> triple [rows][3 seg] of `pattern`, seg >= cols (seg % 8 == 0,
  * columns past cols zero); optional plain bf16 copy hi_out [rows][ld_hi >= seg].  Pattern 2:
  * interleaved pairs [rows][2 seg] (seg % 32 == 0), per 32 columns [hi 32 | lo 32] (the B

@@ -26,16 +26,12 @@ import zlib
 import torch
 
 from dfu_hip import _lib as L
+from dfu_hip.ops import TILE_DIMS  # dfu_gemm_desc.tile -> (TM, TN, phased)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 KERNELS_JSON = os.path.join(HERE, "golden", "gemm_kernels.json")
 
 BF16, F16, F32, F64 = torch.bfloat16, torch.float16, torch.float32, torch.float64
-# dfu_gemm_desc.tile -> (TM, TN, phased): csrc/gemm_table.h DFU_TILES
-TILE_DIMS = {1: (128, 128, False), 2: (256, 128, False), 3: (128, 256, False),
-             4: (256, 256, False), 5: (128, 128, False), 6: (128, 128, False),
-             7: (256, 256, True), 8: (256, 256, True), 9: (192, 256, True),
-             10: (256, 64, False), 11: (128, 64, False)}
 EPS = 2.0 ** -23  # bound on the relative error of one fp32 operation, any rounding mode
 
 GELU_EPIS = (L.EPI_BF16_GELU, L.EPI_X3_GELU, L.EPI_F16_GELU)

@@ -1,9 +1,8 @@
 """Host-side checks that need no GPU: the C ABI library loads and exports every symbol
-include/dfu_hip.h declares, the ctypes descriptor mirrors the C struct byte for byte, argument
-validation fails loudly, the GEMM planner's host logic, and the flat-parameter layout."""
+include/dfu_hip.h declares (the struct layouts: test_abi_cpu.py), argument validation fails
+loudly, the GEMM planner's host logic, and the flat-parameter layout."""
 import ctypes
 import os
-import subprocess
 
 import pytest
 import torch
@@ -20,26 +19,9 @@ def test_library_exports_every_header_symbol():
     assert len(declared) >= 40
     missing = [s for s in declared if not hasattr(lib, s)]
     assert not missing, f"declared in include/dfu_hip.h but not exported: {missing}"
-    assert set(declared) == set(L.PROTOTYPES), "ctypes prototypes out of sync with the header"
+    unbound = [s for s in declared if getattr(lib, s).argtypes != L.FUNCTIONS[s][1]]
+    assert not unbound, f"loaded without the header's argument types: {unbound}"
     assert lib.dfu_version() >= 1
-
-
-def test_gemm_desc_layout_matches_c(tmp_path):
-    fields = [f[0] for f in L.GemmDesc._fields_]
-    src = ['#include <stddef.h>', '#include <stdio.h>', '#include "dfu_hip.h"', "int main(void){",
-           'printf("%zu\\n", sizeof(dfu_gemm_desc));']
-    src += [f'printf("%zu\\n", offsetof(dfu_gemm_desc, {f}));' for f in fields]
-    src += ["return 0;}"]
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(REPO, "include"), str(c), "-o", str(exe)],
-                   check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True,
-                                          text=True).stdout.split()]
-    assert out[0] == ctypes.sizeof(L.GemmDesc)
-    for f, off in zip(fields, out[1:]):
-        assert getattr(L.GemmDesc, f).offset == off, f
 
 
 def _desc(**kw):

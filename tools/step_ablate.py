@@ -21,9 +21,10 @@ import bench  # noqa: E402
 from dfu_hip import _lib as L  # noqa: E402
 from dfu_hip import functional as Fn  # noqa: E402
 from dfu_hip import nn as hnn  # noqa: E402
+from dfu_hip._lib import (EPI_BF16, EPI_BF16_DGELU, EPI_F16_GELU, EPI_F32_ACC,  # noqa: E402
+                          EPI_F32_RESID)
 from dfu_hip.optim import FusedAdamW  # noqa: E402
 
-EPI_BF16, EPI_F32_RESID, EPI_BF16_DGELU, EPI_F32_ACC, EPI_F16_GELU = 0, 4, 5, 7, 15
 # variant -> C-ABI symbols skipped, or ("gemm", predicate on the descriptor)
 VARIANTS = {
     "bn_fin": ["dfu_bn_finalize", "dfu_bn_bwd_finalize"],
@@ -41,9 +42,9 @@ VARIANTS = {
     "gemm_wgrad_vit": ("gemm", lambda d: d.epilogue == EPI_F32_ACC and d.K == 12608),
     "gemm_wgrad_resnet": ("gemm", lambda d: d.epilogue == EPI_F32_ACC and d.K != 12608),
     "gemm_x3pairs": ("gemm", lambda d: bool(d.x3_pairs)),
-    "gemm_dgrad_strided": ("gemm", lambda d: d.a_mode == 3),  # OPND_CONV_DGRAD (stride 2)
+    "gemm_dgrad_strided": ("gemm", lambda d: d.a_mode == L.OPND_CONV_DGRAD),  # stride 2
     "gemm_resnet_dgrad": ("gemm", lambda d: d.M != 12608 and not d.x3_pairs and
-                          d.epilogue in (EPI_BF16, 6)),  # BF16 / BF16_ADD input gradients
+                          d.epilogue in (EPI_BF16, L.EPI_BF16_ADD)),  # input gradients
     "gemm_x3_layer1": ("gemm", lambda d: bool(d.x3_pairs) and d.M == 200704),
     "gemm_x3_deep": ("gemm", lambda d: bool(d.x3_pairs) and d.M < 200704),
     "gemm_f16_gelu": ("gemm", lambda d: d.operand_type == 1 and d.epilogue == EPI_F16_GELU),
