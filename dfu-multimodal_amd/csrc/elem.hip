@@ -1022,6 +1022,7 @@ extern "C" int dfu_maxpool_bwd(const void* dy, const uint8_t* argmax, int32_t B,
                                int32_t W, int32_t C, int32_t P, int32_t Q, void* dx,
                                void* stream) {
   DFU_CHECK_ARG(dy && dx && argmax && C % 8 == 0, "dfu_maxpool_bwd: C %% 8 != 0");
+  DFU_CHECK_ARG(P == (H - 1) / 2 + 1 && Q == (W - 1) / 2 + 1, "dfu_maxpool_bwd: bad P/Q");
   DFU_CHECK_ARG((int64_t)B * ((H + 1) / 2) < 65536 && W * (C / 8) < (1 << 24),
                 "dfu_maxpool_bwd: size");
   const dim3 grid(((W + 1) / 2 * (C / 8) + 255) / 256, B * ((H + 1) / 2));

@@ -485,6 +485,7 @@ extern "C" int dfu_maxpool_fwd_x3(const float* x, int32_t B, int32_t H, int32_t 
                                   void* y_lo, void* y_bf16, uint8_t* argmax, int32_t P, int32_t Q,
                                   void* stream) {
   DFU_CHECK_ARG(x && y_lo && y_bf16 && argmax && C % 8 == 0, "dfu_maxpool_fwd_x3: bad args");
+  DFU_CHECK_ARG(P == (H - 1) / 2 + 1 && Q == (W - 1) / 2 + 1, "dfu_maxpool_fwd_x3: bad P/Q");
   const int64_t n = (int64_t)B * P * Q * (C / 8);
   hipLaunchKernelGGL(k_maxpool_fwd_x3, dim3(nblocks(n)), dim3(TPB), 0, (hipStream_t)stream, x, B,
                      H, W, C, (bf16_t*)y_lo, (bf16_t*)y_bf16, argmax, P, Q);

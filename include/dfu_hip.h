@@ -351,6 +351,7 @@ int dfu_maxpool_fwd(const void* x, int32_t B, int32_t H, int32_t W, int32_t C, v
 int dfu_maxpool_bn_fwd(const void* x, const float* scale, const float* shift, int32_t B,
                        int32_t H, int32_t W, int32_t C, void* y, uint8_t* argmax, int32_t P,
                        int32_t Q, void* stream);
+/* dx [B][H][W][C] bf16 of the pool above; P = (H - 1) / 2 + 1, Q = (W - 1) / 2 + 1 (checked). */
 int dfu_maxpool_bwd(const void* dy, const uint8_t* argmax, int32_t B, int32_t H, int32_t W,
                     int32_t C, int32_t P, int32_t Q, void* dx, void* stream);
 /* resnet AdaptiveAvgPool2d(1) + flatten: NHWC bf16 [B][HW][C] -> fp32 [B][C]. */
@@ -534,7 +535,8 @@ int dfu_bn_apply_x3(const void* y, const void* y_lo, const float* scale, const f
                     const void* residual, const void* residual_lo, int32_t res_mode, int32_t relu,
                     void* out_lo, void* out_bf16, float* out_f32, void* y_bf16,
                     uint8_t* relu_mask, int64_t M, int32_t C, void* stream);
-/* resnet maxpool 3x3/s2/p1 on fp32 NHWC -> split pair (y_bf16 = hi, y_lo) and uint8 argmax. */
+/* resnet maxpool 3x3/s2/p1 on fp32 NHWC -> split pair (y_bf16 = hi, y_lo) and uint8 argmax.
+ * P = (H - 1) / 2 + 1, Q = (W - 1) / 2 + 1 (checked). */
 int dfu_maxpool_fwd_x3(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, void* y_lo,
                        void* y_bf16, uint8_t* argmax, int32_t P, int32_t Q, void* stream);
 /* AdaptiveAvgPool2d(1) on a split pair (hi, lo: [B*HW][C] bf16 each) -> fp32 [B][C]. */
