@@ -14,9 +14,8 @@ Granularity follows the reference's module tree so the nn.Module surface stays d
 Conventions:
   * ResNet activations are bf16 tensors of logical shape (B, C, H, W) in channels_last memory
     (physically NHWC); ViT activations are the fp32 residual stream (B, T, D).
-  * Parameter gradients are ACCUMULATED into persistent ``param.grad`` buffers by the
-    weight-gradient GEMM epilogues (``grad_buffer``), and backward returns None for them: this
-    keeps .grad addresses stable for graph replay, the fused optimizer and bucketed all-reduce.
+  * Parameter gradients go to persistent ``param.grad`` buffers and backward returns None for
+    them (dfu_hip.grads states that protocol).
   * ViT residual-stream gradients are fp32 and modified in place by the LayerNorm backward
     (the producer of every such tensor is a Function in this file).
 """
@@ -31,7 +30,12 @@ from . import ops
 # stream state lives in dfu_hip.streams; the stream accessors stay known by Fn.<name>
 from .streams import (current_stream, join_grad_streams, new_stream, on_stream,  # noqa: F401
                       side_stream, stream_wait, wgrad_stream)
-from .streams import grad_streams as _grad_streams  # grad_buffer stores into it directly
+# gradient plumbing lives in dfu_hip.grads; its names stay known by Fn.<name> as well
+from .grads import (arm_backward_join, disarm_backward_join, grad_buffer,  # noqa: F401
+                    grad_or_none, grads_done, register_backward_end_hook,
+                    register_grad_ready_hook, remove_backward_end_hook, remove_grad_ready_hook,
+                    wants)
+from .optim import x3_pair_weight
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -120,103 +124,6 @@ def _x3(mod=None):
 def _per_stage():
     return _precision[0] in ("mixed", "parity")
 
-# ------------------------------------------------------------------------- grad plumbing
-_grad_ready_hooks = []
-
-
-def register_grad_ready_hook(fn):
-    """fn(param) is called after a Function has finished writing param.grad (DP bucketing)."""
-    _grad_ready_hooks.append(fn)
-    return fn
-
-
-def remove_grad_ready_hook(fn):
-    if fn in _grad_ready_hooks:
-        _grad_ready_hooks.remove(fn)
-
-
-def grad_buffer(p):
-    """Persistent fp32 gradient buffer of parameter p (zeroed on first use); notes the current
-    stream as a gradient producer."""
-    g = p.grad
-    if g is None:
-        g = torch.empty_like(p, memory_format=torch.contiguous_format)
-        ops.zero_(g)
-        p.grad = g
-    if g.is_cuda:
-        st = _current_stream_obj(g)
-        _grad_streams[id(st)] = st
-        # this step's producer stream of p's gradient (False: more than one), for FusedAdamW's
-        # early update of parameters whose gradients are final on a side stream
-        prev = getattr(p, "_dfu_grad_stream", None)
-        p._dfu_grad_stream = st if prev is None or prev is st else False
-    return g
-
-
-def _current_stream_obj(t):
-    """The current stream of t's device as one cached torch Stream object
-    (streams.current_stream; called for every parameter gradient of the step)."""
-    return current_stream(t.get_device())
-
-
-# Parameter gradients are written in place, possibly on a branch's side stream or the ViT
-# weight-gradient stream, which autograd does not synchronise (it only orders the gradients it
-# returns).  So that user code after loss.backward() -- torch.optim optimizers, clip_grad_norm_,
-# manual reductions -- may read every p.grad on the stream that called backward, the first
-# encoder-boundary backward of a graph task (arm_backward_join: the head side of TokenNormFn /
-# AvgPoolFn / ConcatFn, which run on the forward's stream) queues an engine final callback that
-# makes that stream wait for every gradient-producing stream once all backward nodes are
-# enqueued.  Optimizers joined through join_grad_streams anyway (FusedAdamW, GradAllReducer)
-# see no extra wait; any other torch.optim optimizer also joins in a step pre-hook.
-_join_armed = [False]
-_backward_end_hooks = []
-
-
-def register_backward_end_hook(fn):
-    """fn() is called when a backward pass through the HIP encoders has ended (the engine's
-    final callback, after every node ran)."""
-    _backward_end_hooks.append(fn)
-    return fn
-
-
-def remove_backward_end_hook(fn):
-    if fn in _backward_end_hooks:
-        _backward_end_hooks.remove(fn)
-
-
-def arm_backward_join():
-    if _join_armed[0] or not torch.cuda.is_available():
-        return
-    target = current_stream()
-    _join_armed[0] = True
-
-    def _join():
-        _join_armed[0] = False
-        join_grad_streams(target, clear=False)
-        for fn in list(_backward_end_hooks):
-            fn()
-    try:
-        torch.autograd.Variable._execution_engine.queue_callback(_join)
-    except RuntimeError:  # not inside a backward pass (a direct .backward() call of a Function)
-        _join_armed[0] = False
-
-
-def disarm_backward_join():
-    """Forget an armed join whose backward pass a failed graph capture cut short."""
-    _join_armed[0] = False
-
-
-def _optimizer_pre_hook(optimizer, args, kwargs):
-    if _grad_streams and not getattr(optimizer, "_dfu_joins_itself", False):
-        join_grad_streams()
-
-
-try:
-    from torch.optim.optimizer import register_optimizer_step_pre_hook
-    register_optimizer_step_pre_hook(_optimizer_pre_hook)
-except ImportError:  # torch without global optimizer hooks
-    pass
-
 
 # DFU_VIT_WGRAD_STREAM=0: the ViT weight-gradient GEMMs stay on the backward's own stream (A/B)
 _VIT_WGRAD_STREAM = os.environ.get("DFU_VIT_WGRAD_STREAM", "1") != "0"
@@ -256,16 +163,6 @@ class _Beside:
             return fn()
 
 
-def grads_done(*params):
-    if not _grad_ready_hooks:
-        return
-    hooks = tuple(_grad_ready_hooks)  # (a hook may be removed meanwhile: GC)
-    for p in params:
-        if p is not None:
-            for h in hooks:
-                h(p)
-
-
 def module_param(mod, name):
     """mod.<name> for a registered parameter or buffer by its dict (nn.Module.__getattr__, the
     slow path for both, costs ~0.25 us an attribute); anything else by getattr."""
@@ -274,10 +171,6 @@ def module_param(mod, name):
         return p[name]
     b = mod._buffers
     return b[name] if name in b else getattr(mod, name)
-
-
-def wants(p):
-    return p is not None and p.requires_grad
 
 
 def _empty(shape, dtype, device):
@@ -436,7 +329,6 @@ def conv_weight_x3(w):
     launch here); re-split only after an edit outside the optimizer (version counter)."""
     flat = getattr(w, "_dfu_flat", None)
     if _X3_PAIRS and flat is not None:
-        from .optim import x3_pair_weight
         if x3_pair_weight(w):
             if flat.shadow_x3 is None:
                 flat.enable_x3()
@@ -506,8 +398,8 @@ class BNState:
         `out` is not read); or 3 (`out` is the forward's ReLU bitmask, ops.bn_apply(mask=))."""
         bn = self.bn
         w, b = module_param(bn, "weight"), module_param(bn, "bias")
-        dgamma = grad_buffer(w) if wants(w) else None
-        dbeta = grad_buffer(b) if wants(b) else None
+        dgamma = grad_or_none(w)
+        dbeta = grad_or_none(b)
         ops.bn_bwd(dout, y, out, relu, self.mean, self.invstd, w, self.M, self.C, dy,
                    dres, dgamma, dbeta, batch_stats=self.training, scale=self.scale,
                    shift=self.shift)
@@ -992,10 +884,8 @@ class PatchEmbedFn(torch.autograd.Function):
         w, b, cls, pos = ctx.params
         B, T, D, K, C, H, W, ps = ctx.dims
         gX = gX.contiguous()
-        gpatch = ops.vit_embed_bwd(gX, B, T + 1, D,
-                                   grad_buffer(cls) if wants(cls) else None,
-                                   grad_buffer(pos) if wants(pos) else None,
-                                   grad_buffer(b) if wants(b) else None)
+        gpatch = ops.vit_embed_bwd(gX, B, T + 1, D, grad_or_none(cls), grad_or_none(pos),
+                                   grad_or_none(b))
         if wants(w):
             gemm_wgrad(D, K, B * T, gpatch, patches, grad_buffer(w).view(D, K))
         grads_done(w, b, cls, pos)
@@ -1036,8 +926,7 @@ def _ln_bwd(dy_bf, x2d, mean, rstd, norm, rows, D, g, g_bf, gsum=False, batch=No
     """LayerNorm backward; dgamma / dbeta reductions go to `batch` (a PartialReductions) when
     given (the caller reports the parameters done after flushing it)."""
     gsp = ops.layernorm_bwd(dy_bf, D, True, x2d, D, mean, rstd, norm.weight, rows, D, g, D, g_bf,
-                            grad_buffer(norm.weight) if wants(norm.weight) else None,
-                            grad_buffer(norm.bias) if wants(norm.bias) else None, gsum=gsum,
+                            grad_or_none(norm.weight), grad_or_none(norm.bias), gsum=gsum,
                             batch=batch)
     if batch is None:
         grads_done(norm.weight, norm.bias)
@@ -1386,8 +1275,8 @@ class TokenNormFn(torch.autograd.Function):
         gxb = _empty((B, T, D), BF16, x.device)
         ops.zero_(gxb)
         gsp = ops.layernorm_bwd(g, D, False, x, T * D, mean, rstd, norm.weight, B, D, gx, T * D,
-                                gxb, grad_buffer(norm.weight) if wants(norm.weight) else None,
-                                grad_buffer(norm.bias) if wants(norm.bias) else None, gsum=True)
+                                gxb, grad_or_none(norm.weight), grad_or_none(norm.bias),
+                                gsum=True)
         grads_done(norm.weight, norm.bias)
         gx._dfu_bf16 = gxb
         gx._dfu_colsum = gsp  # only the class-token rows are non-zero: their sums are the total

@@ -18,7 +18,7 @@ import sys
 import torch
 
 from . import _lib as L
-from . import functional as Fn
+from . import grads
 from . import streams
 
 
@@ -74,7 +74,7 @@ def reset_after_failed_capture(extra=()):
     cur = torch.cuda.current_stream()
     if cur.cuda_stream in stuck:
         raise RuntimeError("dfu: the caller's stream is still capturing after a failed capture")
-    Fn.disarm_backward_join()
+    grads.disarm_backward_join()
     try:  # can the process run eager work again?  (an allocation + a kernel + a host sync)
         torch.empty(1024, device=cur.device).fill_(0.0)
         torch.cuda.synchronize()

@@ -13,6 +13,7 @@ import torch.distributed as dist
 import torch.nn as tnn
 
 from . import functional as Fn
+from . import grads
 from . import ops
 
 
@@ -208,9 +209,8 @@ class LayerNormFn(torch.autograd.Function):
         ops.zero_(gx)
         ops.layernorm_bwd(g.reshape(rows, D).float().contiguous(), D, False, x2, D, mean, rstd,
                           mod.weight, rows, D, gx, D, None,
-                          Fn.grad_buffer(mod.weight) if Fn.wants(mod.weight) else None,
-                          Fn.grad_buffer(mod.bias) if Fn.wants(mod.bias) else None)
-        Fn.grads_done(mod.weight, mod.bias)
+                          grads.grad_or_none(mod.weight), grads.grad_or_none(mod.bias))
+        grads.grads_done(mod.weight, mod.bias)
         return gx.view(ctx.shape), None, None, None
 
 

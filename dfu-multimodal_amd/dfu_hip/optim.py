@@ -30,7 +30,7 @@ import weakref
 import torch
 import torch.distributed as dist
 
-from . import functional as Fn
+from . import grads
 from . import ops
 from . import streams
 
@@ -309,7 +309,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self.check_grads = True  # set False inside captured graphs (pointers are static)
         # update a side stream's parameter block on that stream (step); DFU_EARLY_ADAMW=0: off
         self.early_update = os.environ.get("DFU_EARLY_ADAMW", "1") != "0"
-        self._dfu_joins_itself = True  # step() joins the gradient streams (functional)
+        grads.mark_self_joining(self)  # step() joins the gradient streams
         # the flat gradient buffer's autograd version at the last zero_grad / step / end of a
         # backward pass: the kernels write gradients through raw pointers (no bump), so a change
         # since means user code edited p.grad in place (clip_grad_norm_, unscaling, a manual
@@ -317,8 +317,8 @@ class FusedAdamW(torch.optim.Optimizer):
         # own AccumulateGrad into a torch.nn head's gradient (the drop-in path) does not count.
         self._grad_version = self.flat.grad._version
         if dev.type == "cuda":
-            hook = Fn.register_backward_end_hook(_version_snapshot(weakref.ref(self)))
-            weakref.finalize(self, Fn.remove_backward_end_hook, hook)
+            hook = grads.register_backward_end_hook(_version_snapshot(weakref.ref(self)))
+            weakref.finalize(self, grads.remove_backward_end_hook, hook)
 
     def zero_grad(self, set_to_none=True):
         # gradients stay bound to the flat buffer (stable addresses); one memset clears them
@@ -332,8 +332,8 @@ class FusedAdamW(torch.optim.Optimizer):
         best, run = None, None
         fp = self.flat
         for i, p in enumerate(fp.params):
-            st = getattr(p, "_dfu_grad_stream", None)
-            st = st if st is not None and st is not False and st != cur else None
+            st = grads.producer(p)
+            st = st if st is not None and st is not grads.MIXED and st != cur else None
             lo, hi = fp.offsets[i], fp.offsets[i] + _aligned(p.numel())
             if st is not None and run is not None and run[2] == st and run[1] == lo:
                 run = (run[0], hi, st)
@@ -399,8 +399,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._adamw(0, early[0])
             if early[1] < fp.numel:
                 self._adamw(early[1], fp.numel)
-        for p in fp.params:
-            p._dfu_grad_stream = None
+        grads.clear_producers(fp.params)
         self.last_early = None if early is None else early[:2]
         fp.shadows_rewritten(None if early is None or fp.t_jobs is None or not _EARLY_T
                              else early[:2])

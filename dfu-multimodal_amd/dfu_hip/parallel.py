@@ -5,7 +5,7 @@ The reference has no distributed code; this adds the one exchange step the path 
 gradient all-reduce of the 110.75M fp32 parameters.  Gradients live in the FusedAdamW flat
 buffer (dfu_hip.optim.FlatParams), so buckets are contiguous slices — no packing copies.
 Buckets are issued in reverse parameter order (the order backward finishes them) on a side
-stream as soon as every parameter of a bucket reports grad-ready (functional.grads_done), so
+stream as soon as every parameter of a bucket reports grad-ready (grads.grads_done), so
 the all-reduce overlaps the rest of the backward pass.  BatchNorm statistics stay per rank
 (no SyncBN), as the reference's single-device BN.
 """
@@ -14,7 +14,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import functional as Fn
+from . import grads
 from . import streams
 
 
@@ -128,7 +128,7 @@ class GradAllReducer:
         self.issue_log = []  # bucket indices in launch order (ranks must agree: RCCL pairs them)
         self.carriers = {}  # stream handle -> stream: the streams this step's collectives used
         if self.overlap:
-            self._hook = Fn.register_grad_ready_hook(self._on_ready)
+            self._hook = grads.register_grad_ready_hook(self._on_ready)
 
     def start(self):
         """Arm the per-step bucket state (call before backward)."""
@@ -147,8 +147,9 @@ class GradAllReducer:
     def _producer(self, p):
         if not self.cuda:
             return None
-        st = getattr(p, "_dfu_grad_stream", None)
-        return st if st else False  # False: several (or unknown) producer streams
+        st = grads.producer(p)
+        # False: several (or unknown) producer streams
+        return False if st is None or st is grads.MIXED else st
 
     def _note(self, k, st):
         if st is False:
@@ -230,5 +231,5 @@ class GradAllReducer:
 
     def close(self):
         if self._hook is not None:
-            Fn.remove_grad_ready_hook(self._hook)
+            grads.remove_grad_ready_hook(self._hook)
             self._hook = None

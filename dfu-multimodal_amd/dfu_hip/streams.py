@@ -5,7 +5,7 @@ of the streams a capture in progress launched on, the library-owned streams (one
 device), the per-stream caches (Stream objects, split-K tile counters) and the set of streams
 that wrote parameter gradients.  dfu_hip.graphs recovers from a failed capture through `forget`
 alone, so a cache added here is reset with the others.  Imports only torch and the loader:
-ops, functional, graphs, optim, parallel and models.fusion import from this module.
+ops, grads, functional, graphs, optim, parallel and models.fusion import from this module.
 """
 import contextlib
 import ctypes
@@ -239,7 +239,7 @@ def tile_counters(device):
 # Streams that wrote persistent parameter gradients since the last join.  Autograd synchronises
 # only the gradients it returns; these buffers are written in place (possibly on a branch's side
 # stream, see models.fusion), so consumers (FusedAdamW.step, GradAllReducer.finish) join first.
-# functional.grad_buffer stores into this dict directly (one dict store per gradient).
+# grads.grad_buffer stores into this dict directly (one dict store per gradient).
 grad_streams = {}
 
 

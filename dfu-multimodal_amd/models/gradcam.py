@@ -26,8 +26,8 @@ sum_b output[b, 0]; in eval mode the images are independent, so each map equals 
 """
 import torch
 
-from dfu_hip import functional as Fn
 from dfu_hip import ops
+from dfu_hip import streams
 
 
 class GradCAM:
@@ -80,7 +80,7 @@ class GradCAM:
             out[:, 0].sum().backward()
         # the ViT blocks' weight gradients may run on the wgrad stream: join it (a graph capture
         # rejects unjoined work, and the next forward's weight reads must follow it)
-        Fn.join_grad_streams()
+        streams.join_grad_streams()
         name = self.target_name()
         if name is None:
             return None

@@ -38,8 +38,8 @@ import os
 import torch
 import torch.distributed as dist
 
-from dfu_hip import functional as Fn
 from dfu_hip import ops
+from dfu_hip import streams
 from models.checkpoint import save_checkpoint
 
 SAVE_BEST_AFTER_EPOCH = 3  # train_multimodal_fusion.py:46
@@ -161,7 +161,7 @@ def run_epoch(model, loader, criterion, optimizer=None, train=True, reducer=None
             loss = criterion(out, labels)
             if train:
                 loss.backward()
-                Fn.join_grad_streams()
+                streams.join_grad_streams()
                 if reducer is not None:
                     reducer.finish()
                 optimizer.step()

@@ -264,7 +264,7 @@ def test_clip_grad_norm_before_fused_adamw_step():
 def test_backward_joins_gradient_streams_for_user_code():
     """After loss.backward() every p.grad is complete on the calling stream, with no explicit
     join: a copy taken right after backward equals the gradients after a full synchronize."""
-    from dfu_hip import functional as Fn
+    from dfu_hip import grads
     from dfu_hip import nn as hnn
     from models.fusion import MultimodalFusionModel
     torch.manual_seed(0)
@@ -278,6 +278,6 @@ def test_backward_joins_gradient_streams_for_user_code():
         loss.backward()
         snap = [p.grad.clone() for p in model.parameters()]  # on s, immediately
     torch.cuda.synchronize()
-    assert not Fn._join_armed[0]
+    assert not grads.join_armed()
     for p, g in zip(model.parameters(), snap):
         assert torch.equal(p.grad, g)

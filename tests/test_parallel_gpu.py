@@ -82,6 +82,7 @@ def _dp_worker(rank, port, overlap, q):
         import bench
         from dfu_hip import functional as Fn
         from dfu_hip import nn as hnn
+        from dfu_hip import streams as dfu_streams
         from dfu_hip.optim import FusedAdamW
         from models.fusion import MultimodalFusionModel
         r, w, _ = parallel.init_from_env(backend="gloo")
@@ -105,7 +106,7 @@ def _dp_worker(rank, port, overlap, q):
             # the streams this step ran gradient work or collectives on (besides the process
             # group's own internal stream)
             streams.clear()
-            streams.update(Fn._grad_streams)
+            streams.update(dfu_streams.grad_streams)
             cur = torch.cuda.current_stream()
             streams[id(cur)] = cur
             if red is not None:

@@ -1,6 +1,6 @@
 """dfu_hip.streams without a GPU: the capture recorder and the guard it arms, and the rule that
-no module of the package reads another module's private stream, ops, functional or graphs
-state."""
+no module of the package reads another module's private stream, ops, functional, graphs or
+grads state."""
 import ast
 import glob
 import os
@@ -11,7 +11,7 @@ from dfu_hip import _lib as L
 from dfu_hip import streams
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OWNERS = ("streams", "ops", "functional", "graphs")
+OWNERS = ("streams", "ops", "functional", "graphs", "grads")
 
 
 def test_the_recorder_arms_the_capture_guard():
