@@ -12,11 +12,11 @@ at a time, the first 5 healthy and the first 5 ulcer samples of each test set:
 Here each model makes one pass over its (up to) ten samples: one batched forward for prediction
 and confidence, one batched GradCAM.generate_cams per encoder, dfu_image_minmax and
 dfu_cam_overlay (ops.cam_overlay) for the three pictures of every sample of a modality, and one
-device -> host read.  OpenCV is not available to this project: the pixel arithmetic is the
-definition in include/dfu_hip.h, restated from OpenCV's documented behaviour, and its agreement
-with cv2 is unverified (tests pin the kernel to a numpy restatement of that definition).  The
-default colour table (ops.jet_lut) has the ends of OpenCV's JET and may differ from it by a level
-or two in between; ops.cam_overlay takes a caller's table.
+device -> host read (evalpass.read_once).  OpenCV is not available to this project: the pixel
+arithmetic is the definition in include/dfu_hip.h, restated from OpenCV's documented behaviour,
+and its agreement with cv2 is unverified (tests pin the kernel to a numpy restatement of that
+definition).  The default colour table (ops.jet_lut) has the ends of OpenCV's JET and may differ
+from it by a level or two in between; ops.cam_overlay takes a caller's table.
 
 Single process only: the pass is not sharded over data-parallel ranks.
 """
@@ -28,6 +28,8 @@ import torch
 from dfu_hip import ops
 from dfu_hip.ops import jet_lut, linear_taps  # noqa: F401  (part of this module's surface)
 from models.gradcam import GradCAM
+
+from .evalpass import read_once
 
 KINDS = ("rgb_only", "thermal_only", "multimodal")
 CLASS_NAMES = ("healthy", "ulcer")  # label 0, 1: the file names
@@ -77,19 +79,6 @@ def select_samples(labels, num_healthy=5, num_ulcer=5):
     return out
 
 
-def _read_once(named):
-    """One device -> host copy of several tensors: {name: numpy array}."""
-    named = sorted(named, key=lambda kv: -kv[1].element_size())  # keeps every offset aligned
-    flat = torch.cat([t.contiguous().view(-1).view(torch.uint8) for _, t in named]).cpu().numpy()
-    out, at = {}, 0
-    for name, t in named:
-        nbytes = t.numel() * t.element_size()
-        dtype = torch.empty(0, dtype=t.dtype).numpy().dtype
-        out[name] = flat[at:at + nbytes].view(dtype).reshape(tuple(t.shape)).copy()
-        at += nbytes
-    return out
-
-
 def visualize_batch(model, kind, rgb=None, thermal=None):
     """visualize_rgb_only / visualize_thermal_only / visualize_multimodal (:465-632) up to the
     figure, for a batch: `kind` in KINDS, `rgb` / `thermal` the normalised fp32 [B, 3, H, W]
@@ -133,7 +122,7 @@ def visualize_batch(model, kind, rgb=None, thermal=None):
     finally:
         for _, grad_cam, _ in jobs:
             grad_cam.remove()
-    return _read_once(named)
+    return read_once(named)
 
 
 def sample_at(batch, i):

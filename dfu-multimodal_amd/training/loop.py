@@ -42,6 +42,8 @@ from dfu_hip import ops
 from dfu_hip import streams
 from models.checkpoint import save_checkpoint
 
+from . import evalpass
+
 SAVE_BEST_AFTER_EPOCH = 3  # train_multimodal_fusion.py:46
 
 
@@ -62,7 +64,8 @@ def _barrier(group=None):
 
 class DeviceMetrics:
     """Epoch accumulators in HBM: confusion int64 [C][C] (row = label, column = prediction),
-    fp64 loss sum, int64 batch count.  update() enqueues one tiny kernel; result() syncs once."""
+    fp64 loss sum, int64 batch count.  update() enqueues one tiny kernel; result() reads the
+    three back in one device -> host copy (evalpass.read_once)."""
 
     def __init__(self, num_classes=2, device="cuda"):
         self.C = num_classes
@@ -80,10 +83,11 @@ class DeviceMetrics:
                 dist.all_reduce(t, group=group)
 
     def result(self):
-        conf = self.confusion.cpu()  # the epoch's one device->host synchronisation
-        loss_sum = float(self.loss_sum.cpu()[0])
-        nb = int(self.batches.cpu()[0])
-        return metrics_from_confusion(conf, loss_sum, nb)
+        # the epoch's one device -> host copy, and with it its one synchronisation
+        host = evalpass.read_once((("confusion", self.confusion), ("loss_sum", self.loss_sum),
+                                   ("batches", self.batches)))
+        return metrics_from_confusion(host["confusion"], float(host["loss_sum"][0]),
+                                      int(host["batches"][0]))
 
 
 def metrics_from_confusion(conf, loss_sum, batches):
@@ -94,24 +98,14 @@ def metrics_from_confusion(conf, loss_sum, batches):
     C = conf.shape[0]
     n = int(conf.sum())
     correct = int(conf.diagonal().sum())
-    out = {"loss": loss_sum / batches if batches else 0.0, "acc": correct / n if n else 0.0,
+    out = {"loss": evalpass.ratio(loss_sum, batches, 0.0), "acc": evalpass.ratio(correct, n, 0.0),
            "n": n, "batches": batches, "confusion": conf.tolist()}
 
     def f1_of(c):
         tp = int(conf[c, c])
-        fp = int(conf[:, c].sum()) - tp
-        fn = int(conf[c, :].sum()) - tp
-        den = 2 * tp + fp + fn
-        return 2 * tp / den if den else 0.0
+        return evalpass.f1_binary(tp, int(conf[:, c].sum()) - tp, int(conf[c, :].sum()) - tp)
     out["f1"] = f1_of(1) if C == 2 else sum(f1_of(c) for c in range(C)) / C
     return out
-
-
-def _forward_fn(model):
-    """model(rgb, thermal) for the fusion model, model(x) otherwise."""
-    def fwd(m, *inputs):
-        return m(*inputs)
-    return fwd
 
 
 def _set_epoch(loader, epoch):
@@ -145,8 +139,9 @@ def run_epoch(model, loader, criterion, optimizer=None, train=True, reducer=None
     reference's step (zero_grad, forward, criterion, backward, optimizer.step; the DP reducer
     brackets backward when given); train=False runs under no_grad in eval mode.  Metrics are
     summed over the ranks of `group` (data parallelism).  collect: a list that receives
-    (logits, labels) per batch (the test phase)."""
-    forward = forward or _forward_fn(model)
+    (logits, labels) per batch (the test phase).  forward(model, *inputs) defaults to
+    evalpass.call_model."""
+    forward = forward or evalpass.call_model
     _check_batch_split(loader)
     model.train(train)
     met = DeviceMetrics(num_classes, device)
@@ -272,8 +267,9 @@ def evaluate(model, loader, criterion, forward=None, num_classes=2, device="cuda
         probs = torch.zeros((0,), dtype=torch.float32, device=device)
         preds = labels = torch.zeros((0,), dtype=torch.int64, device=device)
     preds, labels, probs = gather_in_order((preds, labels, probs), loader, group)
-    res = {"test_preds": list(preds.cpu().numpy()), "test_labels": list(labels.cpu().numpy()),
-           "test_probs": list(probs.cpu().numpy()), "test_acc": r["acc"], "test_f1": r["f1"],
+    host = evalpass.read_once((("preds", preds), ("labels", labels), ("probs", probs)))
+    res = {"test_preds": list(host["preds"]), "test_labels": list(host["labels"]),
+           "test_probs": list(host["probs"]), "test_acc": r["acc"], "test_f1": r["f1"],
            "test_loss": r["loss"]}
     if _is_rank0(group):
         if log:

@@ -10,13 +10,13 @@ plots, :649-867 main):
   roc_auc_score, precision_recall_curve + auc, matthews_corrcoef, cohen_kappa_score,
   roc_curve / precision_recall_curve again for each plot.
 
-Here dfu_tta_reduce (views = 1) gives the probability and decision of every batch on the device,
-dfu_binary_eval_counts the confusion and pair counts and dfu_binary_curve the distinct
-thresholds with their true / false positive counts, and the host reads once at the end.  Every
-metric is then fp64 arithmetic on those integers (numpy; scikit-learn is not needed), following
-scikit-learn 1.7.2's definitions: zero_division=0, the ROC with collinear points dropped, the
-PR-AUC as the trapezoid area of precision over recall (the script's auc(recall, precision), not
-average precision).
+Here dfu_tta_reduce (views = 1) gives the probability and decision of every batch on the device
+(the batch loop is evalpass.predict), dfu_binary_eval_counts the confusion and pair counts and
+dfu_binary_curve the distinct thresholds with their true / false positive counts, and the host
+reads once at the end (evalpass.read_once).  Every metric is then fp64 arithmetic on those
+integers (numpy; scikit-learn is not needed), following scikit-learn 1.7.2's definitions:
+zero_division=0, the ROC with collinear points dropped, the PR-AUC as the trapezoid area of
+precision over recall (the script's auc(recall, precision), not average precision).
 
 Single process only: the pass is not sharded over data-parallel ranks.
 """
@@ -28,18 +28,10 @@ import torch
 
 from dfu_hip import ops
 
+from .evalpass import (GUARD_ZERO, NAN, SKLEARN_ZERO, confusion_2x2, f1_binary, predict, ratio,
+                       read_once)
+
 TARGET_NAMES = ("Healthy", "Ulcer")   # extended_metrics.py:410
-NAN = float("nan")
-
-
-def _div0(num, den):
-    """num / den, 0 where the denominator is 0 (sklearn's zero_division=0)."""
-    return num / den if den else 0.0
-
-
-def _guard0(num, den):
-    """The calculator's own guard (:421-426): the integer 0 when the denominator is 0."""
-    return num / den if den > 0 else 0
 
 
 def _curve_arrays(curve):
@@ -101,8 +93,8 @@ def classification_report(tn, fp, fn, tp):
     rows = []
     for name, hit, pred, true in ((TARGET_NAMES[0], tn, tn + fn, tn + fp),
                                   (TARGET_NAMES[1], tp, tp + fp, tp + fn)):
-        rows.append((name, _div0(hit, pred), _div0(hit, true), _div0(2.0 * hit, true + pred),
-                     as_support(true)))
+        rows.append((name, ratio(hit, pred, SKLEARN_ZERO), ratio(hit, true, SKLEARN_ZERO),
+                     ratio(2.0 * hit, true + pred, SKLEARN_ZERO), as_support(true)))
     vals = np.array([r[1:4] for r in rows], dtype=np.float64)
     support = np.array([r[4] for r in rows], dtype=np.float64)
     macro = vals.mean(axis=0)
@@ -115,7 +107,8 @@ def classification_report(tn, fp, fn, tp):
         text += row_fmt.format(*r, width=width)
     text += "\n"
     text += ("{:>{width}s} " + " {:>9}" * 2 + " {:>9.2f} {:>9}\n").format(
-        "accuracy", "", "", _div0(2.0 * (tn + tp), 2 * n), as_support(n), width=width)
+        "accuracy", "", "", ratio(2.0 * (tn + tp), 2 * n, SKLEARN_ZERO), as_support(n),
+        width=width)
     text += row_fmt.format("macro avg", *macro, as_support(n), width=width)
     text += row_fmt.format("weighted avg", *weighted, as_support(n), width=width)
     return text
@@ -134,19 +127,19 @@ def medical_metrics(counts, curve=None):
     sample, accuracy, mcc and kappa without any sample, kappa when the chance agreement is 1."""
     tn, fp, fn, tp = (int(c) for c in list(counts)[:4])
     n, pos, neg = tn + fp + fn + tp, fn + tp, tn + fp
-    m = {"confusion_matrix": np.array([[tn, fp], [fn, tp]], dtype=np.int64),
+    m = {"confusion_matrix": confusion_2x2(tn, fp, fn, tp),
          "tn": tn, "fp": fp, "fn": fn, "tp": tp,
-         "accuracy": (tn + tp) / n if n else NAN,
-         "precision": _div0(tp, tp + fp),
-         "recall": _div0(tp, pos),
-         "f1": _div0(2.0 * tp, 2 * tp + fp + fn),
+         "accuracy": ratio(tn + tp, n, NAN),
+         "precision": ratio(tp, tp + fp, SKLEARN_ZERO),
+         "recall": ratio(tp, pos, SKLEARN_ZERO),
+         "f1": f1_binary(tp, fp, fn),
          "classification_report": classification_report(tn, fp, fn, tp),
-         "sensitivity": _guard0(tp, tp + fn),
-         "specificity": _guard0(tn, tn + fp),
-         "ppv": _guard0(tp, tp + fp),
-         "npv": _guard0(tn, tn + fn),
-         "fpr": _guard0(fp, fp + tn),
-         "fnr": _guard0(fn, fn + tp)}
+         "sensitivity": ratio(tp, tp + fn, GUARD_ZERO),
+         "specificity": ratio(tn, tn + fp, GUARD_ZERO),
+         "ppv": ratio(tp, tp + fp, GUARD_ZERO),
+         "npv": ratio(tn, tn + fn, GUARD_ZERO),
+         "fpr": ratio(fp, fp + tn, GUARD_ZERO),
+         "fnr": ratio(fn, fn + tp, GUARD_ZERO)}
     if curve is None:
         m["auc_roc"] = m["auc_pr"] = None
     else:
@@ -175,42 +168,24 @@ def medical_metrics(counts, curve=None):
 
 def _evaluate(model, loader, forward=None):
     """evaluate_extended's pass: (result dict, host curve triple)."""
-    forward = forward or (lambda m, *inputs: m(*inputs))
-    model.eval()
-    probs, preds, ys = [], [], []
-    with torch.no_grad():
-        for batch in loader:
-            *inputs, labels = batch
-            out = forward(model, *inputs)
-            if out.dim() != 2 or out.shape[1] not in (1, 2) or out.shape[0] != labels.shape[0]:
-                raise ValueError(f"model output {tuple(out.shape)} for {labels.shape[0]} "
-                                 f"samples: expected [B, 1] or [B, 2]")
-            prob, pred = ops.tta_reduce(out, 1)
-            probs.append(prob)
-            preds.append(pred)
-            ys.append(labels)
-    if not ys:
+    out = predict(model, loader, forward)
+    if out is None:
         empty = (np.zeros(0, np.float32), np.zeros(0, np.int64), np.zeros(0, np.int64))
         return {"y_true": np.zeros(0, np.int64), "y_pred": np.zeros(0, np.int64),
                 "y_probs": np.zeros(0, np.float32),
                 "metrics": medical_metrics([0] * 6, empty)}, empty
-    prob, pred, y = torch.cat(probs), torch.cat(preds), torch.cat(ys).long()
+    prob, pred, y = out
     counts = ops.binary_eval_counts(prob, pred, y)
     thresholds, tps, fps, k = ops.binary_curve(prob, y)
-    n = y.shape[0]
-    # the pass's one device -> host read: counts, K, predictions, labels, probability bits and
-    # the curve (entries past K are not meaningful and are cut below)
-    host = torch.cat([counts, k.long(), pred, y, prob.view(torch.int32).long(),
-                      thresholds.view(torch.int32).long(), tps, fps]).cpu()
-    f32 = lambda t: t.int().view(torch.float32).numpy()  # noqa: E731
-    K = int(host[6])
-    part = [host[7 + i * n:7 + (i + 1) * n] for i in range(6)]
-    y_probs = f32(part[2])
-    if np.isnan(y_probs).any():
+    # the pass's one device -> host read (curve entries past K are not meaningful: cut below)
+    host = read_once((("counts", counts), ("k", k), ("pred", pred), ("y", y), ("prob", prob),
+                      ("thresholds", thresholds), ("tps", tps), ("fps", fps)))
+    if np.isnan(host["prob"]).any():
         raise ValueError("Input contains NaN")
-    curve = (f32(part[3])[:K], part[4].numpy()[:K], part[5].numpy()[:K])
-    return {"y_true": part[1].numpy(), "y_pred": part[0].numpy(), "y_probs": y_probs,
-            "metrics": medical_metrics(host[:6].tolist(), curve)}, curve
+    K = int(host["k"][0])
+    curve = (host["thresholds"][:K], host["tps"][:K], host["fps"][:K])
+    return {"y_true": host["y"], "y_pred": host["pred"], "y_probs": host["prob"],
+            "metrics": medical_metrics(host["counts"], curve)}, curve
 
 
 def evaluate_extended(model, loader, forward=None, results_path=None):

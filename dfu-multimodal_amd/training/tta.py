@@ -17,9 +17,10 @@ of one function):
 Here each image is decoded, copied and resized once, its K views are gathered on the device from
 the one resized image (data.gpu_transforms, views=K; dfu_augment_views), the model runs once per
 loader batch over all batch * K rows, dfu_tta_reduce gives the per-sample mean probability and
-vote, dfu_binary_eval_counts the confusion and AUC pair counts, and the host reads once at the
-end.  A [N, 1] model output is the script's sigmoid head; a [N, 2] output (this repository's
-softmax heads) takes softmax[:, 1] and the argmax per view.
+vote (the batch loop is evalpass.predict), dfu_binary_eval_counts the confusion and AUC pair
+counts, and the host reads once at the end (evalpass.read_once).  A [N, 1] model output is the
+script's sigmoid head; a [N, 2] output (this repository's softmax heads) takes softmax[:, 1] and
+the argmax per view.
 
 Single process only: the pass is not sharded over data-parallel ranks.
 """
@@ -28,12 +29,12 @@ import torch
 
 from dfu_hip import ops
 
+from .evalpass import NAN, confusion_2x2, f1_binary, predict, ratio, read_once
+
 ROBUST_BELOW = 0.05     # test_time_augmentation.py:430
 MODERATE_BELOW = 0.15   # :432
-
-
-def _ratio(num, den):
-    return num / den if den else float("nan")
+_SHAPE_ERROR = ("model output {shape} for {samples} samples of {views} views: "
+                "expected [N, 1] or [N, 2]")
 
 
 def metrics_from_counts(counts, predictions, probabilities, labels):
@@ -44,14 +45,13 @@ def metrics_from_counts(counts, predictions, probabilities, labels):
     divide by zero)."""
     tn, fp, fn, tp, greater, ties = (int(c) for c in counts)
     n, pos, neg = tn + fp + fn + tp, fn + tp, tn + fp
-    f1_den = 2 * tp + fp + fn
     return {
-        "accuracy": _ratio(tn + tp, n),
-        "f1": 2 * tp / f1_den if f1_den else 0.0,
-        "auc": _ratio(greater + 0.5 * ties, pos * neg),
-        "sensitivity": _ratio(tp, pos),
-        "specificity": _ratio(tn, neg),
-        "confusion_matrix": np.array([[tn, fp], [fn, tp]], dtype=np.int64),
+        "accuracy": ratio(tn + tp, n, NAN),
+        "f1": f1_binary(tp, fp, fn),
+        "auc": ratio(greater + 0.5 * ties, pos * neg, NAN),
+        "sensitivity": ratio(tp, pos, NAN),
+        "specificity": ratio(tn, neg, NAN),
+        "confusion_matrix": confusion_2x2(tn, fp, fn, tp),
         "predictions": np.asarray(predictions),
         "probabilities": np.asarray(probabilities),
         "labels": np.asarray(labels),
@@ -77,33 +77,15 @@ def evaluate_tta(model, loader, num_tta=5, use_augmentation=True, forward=None,
     if specs and any(s.random for s in specs) != bool(use_augmentation):
         raise ValueError(f"use_augmentation = {use_augmentation}, but the loader's transforms "
                          f"are {'random' if specs[0].random else 'not random'}")
-    forward = forward or (lambda m, *inputs: m(*inputs))
-    model.eval()
-    probs, preds, ys = [], [], []
-    with torch.no_grad():
-        for batch in loader:
-            *inputs, labels = batch
-            out = forward(model, *inputs)
-            if out.dim() != 2 or out.shape[1] not in (1, 2) or \
-                    out.shape[0] != labels.shape[0] * num_tta:
-                raise ValueError(f"model output {tuple(out.shape)} for {labels.shape[0]} "
-                                 f"samples of {num_tta} views: expected [N, 1] or [N, 2]")
-            prob, pred = ops.tta_reduce(out, num_tta)
-            probs.append(prob)
-            preds.append(pred)
-            ys.append(labels)
-    if not ys:
+    out = predict(model, loader, forward, num_tta, _SHAPE_ERROR)
+    if out is None:
         res = metrics_from_counts([0] * 6, np.zeros(0, np.int64), np.zeros(0, np.float32),
                                   np.zeros(0, np.int64))
     else:
-        prob, pred, y = torch.cat(probs), torch.cat(preds), torch.cat(ys).long()
+        prob, pred, y = out
         counts = ops.binary_eval_counts(prob, pred, y)
-        n = y.shape[0]
-        # the pass's one device -> host read: counts, predictions, labels and probability bits
-        host = torch.cat([counts, pred, y, prob.view(torch.int32).long()]).cpu()
-        res = metrics_from_counts(host[:6].tolist(), host[6:6 + n].numpy(),
-                                  host[6 + 2 * n:].int().view(torch.float32).numpy(),
-                                  host[6 + n:6 + 2 * n].numpy())
+        host = read_once((("counts", counts), ("pred", pred), ("y", y), ("prob", prob)))
+        res = metrics_from_counts(host["counts"], host["pred"], host["prob"], host["y"])
     if results_path is not None:
         torch.save(res, results_path)
     return res
