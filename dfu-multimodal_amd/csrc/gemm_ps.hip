@@ -20,7 +20,7 @@
 namespace dfu {
 namespace {
 
-// Timing ablations (tools/build_ablate.sh builds a separate library with -DDFU_PS_ABLATE=mask;
+// Timing ablations (tools/build_exp.sh builds a separate library with -DDFU_PS_ABLATE=mask;
 // the product build is 0): 1 no epilogue, 2 no MFMA, 4 no DMA, 8 no fragment reads (zero
 // fragments), 16 no K-step barrier, 32 epilogue accesses out of range (issued, no traffic),
 // 64 / 128 no B DMA / no B fragment reads, 256 / 512 the same for A.  The DMA and read

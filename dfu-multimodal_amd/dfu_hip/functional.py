@@ -974,7 +974,7 @@ def _linear_dgrad(rows, N, K, g, weight, w_rows, out, epilogue=L.EPI_BF16, **kw)
 _X3_TILE = int(os.environ.get("DFU_X3_TILE", "8"))
 # The GEMMs to D = 768 columns (proj and fc2 forward, the fc1 / proj / qkv input gradients) run
 # on the persistent 192 x 256 tile (tile 9: 198 tiles at M = 12608 instead of 150 of 256 rows
-# for 256 CUs; 8-16 % faster standalone, tools/gpu_tile192.sh) when the ViT runs alone.  Inside
+# for 256 CUs; 8-16 % faster standalone, tools/gemm_one.py --tile 9) when the ViT runs alone.  Inside
 # the two-stream fusion step the 256-row tile's idle CUs run the ResNet's kernels: there tile 9
 # measured 19.11 vs 18.97 ms per step (same box, three rounds), so it keeps the 256-row plan.
 # (The parity mode's fp16 proj / fc2 follow their own tuned entries, tile 9: 20.79-20.85 vs

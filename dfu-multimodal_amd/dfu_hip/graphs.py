@@ -35,7 +35,7 @@ def join_forked(origin, extra=()):
     fork of this capture), so work left on a side stream joins the graph instead of failing
     the capture as unjoined -- which HIP cannot undo: the origin's hipStreamEndCapture then
     returns hipErrorStreamCaptureUnjoined and leaves the origin and its forks capturing for
-    good (a second end returns hipErrorStreamCaptureWrongThread; tools/diag).  The step streams
+    good (a second end returns hipErrorStreamCaptureWrongThread).  The step streams
     include every stream a library launch went to during this capture, so a fork onto a plain
     torch stream that the step did not join back (the C5 split-graph
     attempt's crash at hipStreamEndCapture) is joined here too; only non-library work on a
@@ -63,9 +63,9 @@ def abort_captures(known):
 
 def reset_after_failed_capture(extra=()):
     """Recover after a failed capture: end what HIP lets us end, retire the library-owned
-    streams still capturing (HIP cannot end a capture whose origin's end already failed:
-    tools/diag/capture_unjoined.py) -- the next side_stream / wgrad_stream / capture_stream call
-    makes fresh ones -- and reset the host-side stream state (streams.forget).  Returns (streams
+    streams still capturing (HIP cannot end a capture whose origin's end already failed: the
+    origin and its forks keep reporting an active capture, see join_forked) -- the next
+    side_stream / wgrad_stream / capture_stream call makes fresh ones -- and reset the host-side stream state (streams.forget).  Returns (streams
     that were capturing, streams retired)."""
     known = streams.known_streams(extra=extra)
     n, _ = abort_captures(known)

@@ -2,6 +2,9 @@
 # Experiment build of one translation unit with extra defines, linked with the product objects
 # into dfu_hip/libdfu_exp_<tag>.so (select at run time with DFU_HIP_LIB=...).
 #   bash tools/build_exp.sh <tag> <source stem> "-DMACRO=1 ..."
+# The timing ablations of the persistent phased GEMM (results wrong by design; tools/gemm_ablate.py):
+#   bash tools/build_exp.sh ablate_<mask> gemm_ps -DDFU_PS_ABLATE=<mask>
+# -> dfu_hip/libdfu_exp_ablate_<mask>.so (formerly build_ablate.sh's dfu_hip/libdfu_ablate_<mask>.so)
 set -e
 cd "$(dirname "$0")/../dfu-multimodal_amd"
 make -j8 >/dev/null

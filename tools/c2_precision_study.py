@@ -9,16 +9,12 @@ import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT]
-import torch  # noqa: E402
-import torch.nn as nn  # noqa: E402
+import _harness  # noqa: F401
+import torch
+import torch.nn as nn
 
-from oracle import torch_ref as R  # noqa: E402
+from oracle import torch_ref as R
 
-torch.set_num_threads(int(os.environ.get("THREADS", "8")))
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-seeds = [int(s) for s in (sys.argv[2] if len(sys.argv) > 2 else "0,1,2").split(",")]
 SITES = ("ln1", "ln1_w", "qkv", "p", "attn_out", "attn_out_w", "ln2", "ln2_w", "gelu", "gelu_w")
 W = ("ln1_w", "attn_out_w", "ln2_w", "gelu_w")
 
@@ -44,8 +40,6 @@ CASES = {
 }
 for site in SITES:
     CASES[f"{site} exact"] = policy((), (site,))
-if len(sys.argv) > 3:
-    CASES = {k: v for k, v in CASES.items() if k in sys.argv[3].split(";")}
 
 
 def run(vit, x, pol):
@@ -64,21 +58,32 @@ def run(vit, x, pol):
         R.set_bf16_emulation(False)
 
 
-res = {k: [] for k in CASES}
-for s in seeds:
-    torch.manual_seed(s)
-    vit = R.VisionTransformer(num_classes=2)
-    vit.head = nn.Sequential(nn.Dropout(0.0), nn.Linear(768, 2))
-    vit.train()
-    _, th, _ = R.synthetic_batch(B, seed=42 + s)
-    t0 = time.time()
-    f32 = run(vit, th, [])
-    print(f"seed {s} B={B}: max|logit| {f32.abs().max():.4f} ({time.time() - t0:.0f} s)",
-          flush=True)
-    for name, pol in CASES.items():
-        d = (run(vit, th, pol) - f32).abs().max().item()
-        res[name].append(d)
-        print(f"  {name:32s}: max|dlogit| {d:.3e}", flush=True)
-print("summary (worst over seeds):")
-for name, ds in res.items():
-    print(f"  {name:32s}: {max(ds):.3e}  [{' '.join(f'{d:.2e}' for d in ds)}]")
+def main():
+    torch.set_num_threads(int(os.environ.get("THREADS", "8")))
+    B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+    seeds = [int(s) for s in (sys.argv[2] if len(sys.argv) > 2 else "0,1,2").split(",")]
+    cases = CASES
+    if len(sys.argv) > 3:
+        cases = {k: v for k, v in CASES.items() if k in sys.argv[3].split(";")}
+    res = {k: [] for k in cases}
+    for s in seeds:
+        torch.manual_seed(s)
+        vit = R.VisionTransformer(num_classes=2)
+        vit.head = nn.Sequential(nn.Dropout(0.0), nn.Linear(768, 2))
+        vit.train()
+        _, th, _ = R.synthetic_batch(B, seed=42 + s)
+        t0 = time.time()
+        f32 = run(vit, th, [])
+        print(f"seed {s} B={B}: max|logit| {f32.abs().max():.4f} ({time.time() - t0:.0f} s)",
+              flush=True)
+        for name, pol in cases.items():
+            d = (run(vit, th, pol) - f32).abs().max().item()
+            res[name].append(d)
+            print(f"  {name:32s}: max|dlogit| {d:.3e}", flush=True)
+    print("summary (worst over seeds):")
+    for name, ds in res.items():
+        print(f"  {name:32s}: {max(ds):.3e}  [{' '.join(f'{d:.2e}' for d in ds)}]")
+
+
+if __name__ == "__main__":
+    main()

@@ -4,17 +4,8 @@ calling site in this repository.
 
   python tools/copy_sites.py
 """
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dfu-multimodal_amd")]
-import torch  # noqa: E402
-
-import bench  # noqa: E402
-from dfu_hip import functional as Fn  # noqa: E402
-from dfu_hip import nn as hnn  # noqa: E402
-from dfu_hip.optim import FusedAdamW  # noqa: E402
+import _harness
+import torch
 
 OPS = ("aten::copy_", "aten::clone", "aten::contiguous", "aten::to", "aten::_to_copy",
        "aten::fill_", "aten::zero_", "aten::zeros", "aten::zeros_like", "aten::cat",
@@ -22,18 +13,7 @@ OPS = ("aten::copy_", "aten::clone", "aten::contiguous", "aten::to", "aten::_to_
 
 
 def main():
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(42)
-    model, fwd = bench.build("fusion", dev)
-    opt = FusedAdamW(model.parameters(), lr=1e-4, weight_decay=1e-4)
-    crit = hnn.CrossEntropyLoss(weight=torch.tensor([2.0, 2.0], device=dev))
-    rgb, th, y = bench.synthetic(64, dev, seed=42)
-
-    def step():
-        opt.zero_grad()
-        crit(fwd(model, rgb, th), y).backward()
-        Fn.join_grad_streams()
-        opt.step()
+    step = _harness.fusion_step().step
     for _ in range(3):
         step()
     torch.cuda.synchronize()

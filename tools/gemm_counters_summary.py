@@ -1,4 +1,4 @@
-"""MFMA-utilisation table of single GEMM shapes from tools/gemm_counters_r3.sh output.
+"""MFMA-utilisation table of single GEMM shapes from tools/profile.sh counters output.
 
   python tools/gemm_counters_summary.py gpurun_out/ctr [gpurun_out/actr] > profiles/r21_gemm_counters.md
 
@@ -14,8 +14,8 @@ GEMM dispatch of the two --pmc passes (averaged over the 6 dispatches of each ru
                  and SQ_ACTIVE_INST_ANY as shares of SQ_WAVE_CYCLES;
   * LDS        = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE, SQ_WAIT_INST_LDS / SQ_WAVE_CYCLES, and
                  SQ_INSTS_LDS / SQ_INSTS_MFMA.
-With a second directory (tools/attn_counters.sh output) the attention kernels follow (counters
-only).
+With a second directory (tools/profile.sh counters actr/ -- python3 tools/kernel_time.py attn)
+the attention kernels follow (counters only).
 """
 import csv
 import glob
@@ -52,7 +52,7 @@ def main():
     times = {}
     for ln in open(os.path.join(root, "times.txt")):
         m = re.match(r"(\S+) tile (\d+): ([\d.]+) us\s+(\d+) TFLOP/s", ln.strip())
-        if m:  # run directories: <case>_t<tile>_{a,b} (tools/gemm_counters.sh)
+        if m:  # run directories: <case>_t<tile>_{a,b} (tools/profile.sh counters ctr/<case>_t<tile>)
             times[f"{m.group(1)}_t{m.group(2)}"] = (float(m.group(3)), float(m.group(4)))
     print("# MFMA utilisation of the step's top GEMM shapes (rocprofv3 --pmc, one MI355X)\n")
     print(__doc__.split("\n\n", 1)[1].strip() + "\n")
@@ -65,7 +65,7 @@ def main():
         if not a:
             continue
         rows(case, us, tf, a, b)
-    if len(sys.argv) > 2:  # tools/attn_counters.sh output: the attention kernels (no time here)
+    if len(sys.argv) > 2:  # the attention passes: the attention kernels (no time here)
         for pat in ("k_attn_fwd", "k_attn_bwd"):
             a = dispatch_counters(os.path.join(sys.argv[2], "a"), pat)
             b = dispatch_counters(os.path.join(sys.argv[2], "b"), pat)

@@ -8,15 +8,12 @@
          l1c3x3_fwd / l1c1x3_fwd / l3c2x3_fwd (bf16x3 pair convs; FLOPs: the MFMA work, 3 products)
 """
 import argparse
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dfu-multimodal_amd")]
-import torch  # noqa: E402
+import _harness
+import torch
 
-from dfu_hip import _lib as L  # noqa: E402
-from dfu_hip import ops  # noqa: E402
+from dfu_hip import _lib as L
+from dfu_hip import ops
 
 
 def T(*s, dtype=torch.bfloat16):
@@ -26,36 +23,44 @@ def T(*s, dtype=torch.bfloat16):
 CHECK = []  # (HIP result, fp32 reference) thunks for --check
 
 
+def vit(case):
+    """(M, N, K) of a ViT case <layer>_<kind>: the forward's _harness.VIT_SHAPES entry, N and K
+    swapped for an input gradient, N x K x M for a weight gradient."""
+    layer, kind = case.split("_", 1)
+    M, N, K = _harness.VIT_SHAPES[layer.replace("x3", "")]
+    if kind.startswith("dgrad"):
+        return M, K, N
+    return (N, K, M) if kind == "wgrad" else (M, N, K)
+
+
 def build(case, tile):
     if case in ("qkv_fwd", "proj_fwd", "fc2_fwd"):
-        M, N, K = {"qkv_fwd": (12608, 2304, 768), "proj_fwd": (12608, 768, 768),
-                   "fc2_fwd": (12608, 768, 3072)}[case]
+        M, N, K = vit(case)
         A, B, C = T(M, K), T(N, K), T(M, N)
         bias = T(N, dtype=torch.float32)
         CHECK.append(lambda: (C.float(), A.float() @ B.float().t() + bias))
         return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, K, B, K, C, N, epilogue=L.EPI_BF16,
                                                bias=bias, tile=tile)
     if case in ("fc1_fwd", "fc1_gelu"):
-        M, N, K = 12608, 3072, 768
+        M, N, K = vit("fc1_fwd")
         A, B, C, pre = T(M, K), T(N, K), T(M, N), T(M, N)
         epi = L.EPI_BF16_GELU if case == "fc1_gelu" else L.EPI_BF16
         kw = dict(aux_out=pre, ldaux_out=N) if case == "fc1_gelu" else {}
         return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, K, B, K, C, N, epilogue=epi, tile=tile, **kw)
     if case == "fc2_dgrad":
-        M, N, K = 12608, 3072, 768
+        M, N, K = vit(case)
         A, B, C, h = T(M, K), T(K, N), T(M, N), T(M, N)
         return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, K, B, N, C, N, b_mode=L.OPND_MNMAJOR,
                                                epilogue=L.EPI_BF16_DGELU, aux=h, ldaux=N, tile=tile)
     if case in ("fc1_dgrad", "qkv_dgrad"):
-        M, N, K = {"fc1_dgrad": (12608, 768, 3072), "qkv_dgrad": (12608, 768, 2304)}[case]
+        M, N, K = vit(case)
         A, B, C = T(M, K), T(K, N), T(M, N)
         CHECK.append(lambda: (C.float(), A.float() @ B.float()))
         return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, K, B, N, C, N, b_mode=L.OPND_MNMAJOR,
                                                epilogue=L.EPI_BF16, tile=tile)
-    if case in ("fc1_dgrad_t", "qkv_dgrad_t", "fc2_dgrad_t"):
+    if case in ("fc1_dgrad_t", "qkv_dgrad_t", "fc2_dgrad_t", "proj_dgrad_t"):
         # the dgrads with a pre-transposed weight: B K-contiguous (KM x KM)
-        M, N, K = {"fc1_dgrad_t": (12608, 768, 3072), "qkv_dgrad_t": (12608, 768, 2304),
-                   "fc2_dgrad_t": (12608, 3072, 768)}[case]
+        M, N, K = vit(case)
         A, B, C, h = T(M, K), T(N, K), T(M, N), T(M, N)
         if case == "fc2_dgrad_t":
             return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, K, B, K, C, N,
@@ -64,15 +69,10 @@ def build(case, tile):
         CHECK.append(lambda: (C.float(), A.float() @ B.float().t()))
         return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, K, B, K, C, N, epilogue=L.EPI_BF16,
                                                tile=tile)
-    if case == "proj_dgrad_t":
-        M, N, K = 12608, 768, 768
-        A, B, C = T(M, K), T(N, K), T(M, N)
-        CHECK.append(lambda: (C.float(), A.float() @ B.float().t()))
-        return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, K, B, K, C, N, epilogue=L.EPI_BF16,
-                                               tile=tile)
-    if case in ("proj_fwd_resid", "fc2x3_fwd_resid", "projx3_fwd_resid"):
-        M, N, K = {"proj_fwd_resid": (12608, 768, 768), "fc2x3_fwd_resid": (12608, 768, 9216),
-                   "projx3_fwd_resid": (12608, 768, 2304)}[case]
+    if case in ("proj_fwd_resid", "fc2_fwd_resid", "fc2x3_fwd_resid", "projx3_fwd_resid"):
+        # fc2_fwd_resid is the step's fc2 forward (fp32 residual-stream epilogue); x3: K tripled
+        M, N, K = vit(case)
+        K *= 3 if "x3" in case else 1
         A, B = T(M, K), T(N, K)
         C, X = T(M, N, dtype=torch.float32), T(M, N, dtype=torch.float32)
         bias = T(N, dtype=torch.float32)
@@ -80,28 +80,12 @@ def build(case, tile):
         return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, K, B, K, C, N,
                                                epilogue=L.EPI_F32_RESID, bias=bias, aux=X,
                                                ldaux=N, tile=tile)
-    if case == "fc2_fwd_resid":  # the step's fc2 forward: fp32 residual-stream epilogue
-        M, N, K = 12608, 768, 3072
-        A, B = T(M, K), T(N, K)
-        C, X = T(M, N, dtype=torch.float32), T(M, N, dtype=torch.float32)
-        bias = T(N, dtype=torch.float32)
-        CHECK.append(lambda: (C - X, A.float() @ B.float().t() + bias))
-        return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, K, B, K, C, N,
-                                               epilogue=L.EPI_F32_RESID, bias=bias, aux=X,
-                                               ldaux=N, tile=tile)
-    if case in ("fc2_wgrad", "qkv_wgrad", "proj_wgrad"):
-        M, N, K = {"fc2_wgrad": (768, 3072, 12608), "qkv_wgrad": (2304, 768, 12608),
-                   "proj_wgrad": (768, 768, 12608)}[case]
+    if case in ("fc1_wgrad", "fc2_wgrad", "qkv_wgrad", "proj_wgrad"):
+        M, N, K = vit(case)
         A, B = T(K, M), T(K, N)
         C = torch.zeros(M, N, device="cuda")
-        CHECK.append(lambda: (C.clone(), A.float().t() @ B.float()))
-        return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, M, B, N, C, N, a_mode=L.OPND_MNMAJOR,
-                                               b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC,
-                                               tile=tile)
-    if case == "fc1_wgrad":
-        M, N, K = 3072, 768, 12608
-        A, B = T(K, M), T(K, N)
-        C = torch.zeros(M, N, device="cuda")
+        if case != "fc1_wgrad":
+            CHECK.append(lambda: (C.clone(), A.float().t() @ B.float()))
         return 2 * M * N * K, lambda: ops.gemm(M, N, K, A, M, B, N, C, N, a_mode=L.OPND_MNMAJOR,
                                                b_mode=L.OPND_MNMAJOR, epilogue=L.EPI_F32_ACC,
                                                tile=tile)
@@ -155,13 +139,7 @@ def main():
         if not err < 1e-2:
             raise SystemExit(f"{a.case}: CHECK FAILED")
         return
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(a.iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    us = e0.elapsed_time(e1) * 1e3 / a.iters
+    us = _harness.time_us(fn, a.iters, 0)
     print(f"{a.case} tile {a.tile}: {us:.1f} us  {flops / us / 1e6:.0f} TFLOP/s")
 
 

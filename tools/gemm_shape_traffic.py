@@ -16,16 +16,14 @@ run; its per-shape times replace the ones recorded in shapes.json, which were ta
 import collections
 import csv
 import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "dfu-multimodal_amd")]
-from dfu_hip import ops  # noqa: E402
+import _harness
 
-OPND = ["KM", "MN", "CFWD", "CDGD", "CDGW", "CWGX"]
-EPI = ["BF16", "RELU", "GELU", "F32", "RESID", "DGELU", "ADD", "ACC", "ACCW", "STATS", "PATCH",
-       "F32STATS", "DSTATS", "X3GELU", "F16DUAL", "F16GELU"]
+from dfu_hip import ops
+
+OPND = [short for short, _ in _harness.OPND_NAMES]
+EPI = [short for short, _ in _harness.EPI_NAMES]
 TILE = list(ops.TILES)  # in id order
 
 

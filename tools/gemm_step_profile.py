@@ -7,40 +7,14 @@ floor (compulsory bytes / 6 TB/s).
 """
 import argparse
 import ctypes
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dfu-multimodal_amd")]
-import torch  # noqa: E402
+import _harness
+import torch
+from _harness import gemm_key, gemm_label, time_desc
 
-import bench  # noqa: E402
-from dfu_hip import _lib as L  # noqa: E402
-from dfu_hip import ops  # noqa: E402
+from dfu_hip import ops
 
-OPND = ["KM", "MN", "CFWD", "CDGD", "CDGW", "CWGX"]
-EPI = ["BF16", "RELU", "GELU", "F32", "RESID", "DGELU", "ADD", "ACC", "ACCW", "STATS", "PATCH", "F32STATS",
-       "DSTATS", "X3GELU", "F16DUAL", "F16GELU"]
 TILE = list(ops.TILES)  # in id order
-
-
-def key(d):
-    return (d.a_mode, d.b_mode, d.epilogue, d.M, d.N, d.K, d.conv_n, d.conv_h, d.conv_w, d.conv_c,
-            d.conv_k, d.conv_r, d.conv_s, d.conv_stride, d.conv_pad, d.operand_type)
-
-
-def time_desc(d, iters):
-    lib = ops.lib()
-    s = ops.stream_ptr()
-    for _ in range(2):
-        ops.check(lib.dfu_gemm(ctypes.byref(d), s), "dfu_gemm")
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        lib.dfu_gemm(ctypes.byref(d), s)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters
 
 
 def main():
@@ -58,24 +32,10 @@ def main():
                          "launch order) to this JSON for tools/gemm_shape_traffic.py")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    torch.manual_seed(42)
-    from dfu_hip import nn as hnn
-    from dfu_hip.optim import FusedAdamW
-    model, fwd = bench.build(a.config, dev)
-    opt = FusedAdamW(model.parameters(), lr=1e-4, weight_decay=1e-4)
-    crit = hnn.CrossEntropyLoss(weight=torch.tensor([2.0, 2.0], device=dev))
-    rgb, th, y = bench.synthetic(a.batch, dev, 42)
-    from dfu_hip import functional as Fn
-    ops.gemm_record = []
-    opt.zero_grad()
-    with Fn.precision(a.precision):
-        crit(fwd(model, rgb, th), y).backward()
-    opt.step()
-    rec, ops.gemm_record = ops.gemm_record, None
-    torch.cuda.synchronize()
+    rec = _harness.record_step_gemms(_harness.fusion_step(a.config, a.batch), a.precision)
     uniq = {}
     for d, flops, nbytes, refs, _ in rec:
-        e = uniq.setdefault(key(d), [d, flops, nbytes, refs, 0])
+        e = uniq.setdefault(gemm_key(d), [d, flops, nbytes, refs, 0])
         e[4] += 1
     rows = []
     marks = []
@@ -84,7 +44,7 @@ def main():
         if a.markers:
             torch.cuda.synchronize()
             ops.argmax_rows(mk)  # segment delimiter in the dispatch trace
-            marks.append({"key": list(key(d)), "per_step": n, "flops": flops, "bytes": nbytes,
+            marks.append({"key": list(gemm_key(d)), "per_step": n, "flops": flops, "bytes": nbytes,
                           "launches": 2 + a.iters})
         us = time_desc(d, a.iters)
         us1 = None
@@ -117,7 +77,7 @@ def main():
           f"{fl / tot / 1e6:.0f} TFLOP/s")
     print(f"{'ms/step':>8} {'n':>3} {'us':>7} {'1shot':>7} {'TF/s':>5} {'hbm_us':>6}  plan  shape")
     for tot_us, n, us, us1, flops, nbytes, d, t, sk in rows:
-        name = (f"{OPND[d.a_mode]}x{OPND[d.b_mode]}->{EPI[d.epilogue]} {d.M}x{d.N}x{d.K}"
+        name = (f"{gemm_label(d)} {d.M}x{d.N}x{d.K}"
                 + (f" conv{d.conv_h}x{d.conv_w} c{d.conv_c} k{d.conv_k} r{d.conv_r} s{d.conv_stride}"
                    if d.conv_n else "") + (" f16" if d.operand_type else ""))
         print(f"{tot_us / 1e3:8.3f} {n:3d} {us:7.1f} {us1 if us1 is not None else 0:7.1f} "

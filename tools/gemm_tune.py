@@ -11,26 +11,20 @@ over the analytic cost model (csrc/gemm.hip), so plans are deterministic (no run
 import argparse
 import ctypes
 import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dfu-multimodal_amd")]
-import torch  # noqa: E402
+import _harness
+import torch
+from _harness import CONV_FIELDS, copy_desc, gemm_label, time_desc
 
-import bench  # noqa: E402
-from dfu_hip import _lib as L  # noqa: E402
-from dfu_hip import ops  # noqa: E402
+from dfu_hip import _lib as L
+from dfu_hip import ops
 
 SPLITS = [1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64, 96, 128, 192, 256]
-OPND = ["KM", "MN", "CONV_FWD", "CONV_DGRAD", "CONV_DGRAD_W", "CONV_WGRAD_X"]
-EPI = ["BF16", "BF16_RELU", "BF16_GELU", "F32", "F32_RESID", "BF16_DGELU", "BF16_ADD", "F32_ACC",
-       "F32_ACC_CONVW", "BF16_STATS", "PATCH", "F32_STATS", "BF16_DSTATS", "X3_GELU", "F16_DUAL", "F16_GELU"]
-CONV_FIELDS = ("conv_n", "conv_h", "conv_w", "conv_c", "conv_k", "conv_r", "conv_s",
-               "conv_stride", "conv_pad")
 
 
-def key(d):
+def table_key(d):
+    """The key fields of a gemm_tuned.inc entry."""
     conv = d.a_mode >= L.OPND_CONV_FWD or d.b_mode >= L.OPND_CONV_FWD
     # the table's epilogue field is the dispatch key (| 128: interleaved bf16x3 pairs, | 64: fp16
     # operands -- whose lookup falls back to the bf16 entry of the same shape)
@@ -39,40 +33,12 @@ def key(d):
         tuple(getattr(d, f) for f in CONV_FIELDS) if conv else (0,) * 9)
 
 
-def copy_desc(d):
-    n = L.GemmDesc()
-    ctypes.memmove(ctypes.byref(n), ctypes.byref(d), ctypes.sizeof(d))
-    return n
-
-
-def time_desc(d, iters, ws):
-    lib = ops.lib()
-    need = lib.dfu_gemm_workspace_bytes(ctypes.byref(d))
-    if need > ws.numel():
-        ws = torch.empty(need, dtype=torch.uint8, device="cuda")
-    d.workspace = ws.data_ptr() if need > 0 else None
-    d.workspace_bytes = int(need)
-    cnt = ops.tile_counters(torch.device("cuda", 0))  # split-K / tail-split hand-off counters
-    d.tile_counters, d.tile_counters_len = cnt.data_ptr(), cnt.numel()
-    s = ops.stream_ptr()
-    for _ in range(2):
-        ops.check(lib.dfu_gemm(ctypes.byref(d), s), "dfu_gemm")
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        lib.dfu_gemm(ctypes.byref(d), s)
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / iters, ws
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--config", default="fusion")
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "dfu-multimodal_amd", "csrc",
-                                                  "gemm_tuned.inc"))
+    ap.add_argument("--out", default=os.path.join(_harness.PKG, "csrc", "gemm_tuned.inc"))
     ap.add_argument("--append", action="store_true", help="keep entries already in --out")
     ap.add_argument("--tiles", default="1-11", help="tile ids to try, e.g. 1-11 or 6,8")
     ap.add_argument("--precision", default="bf16", help="record the step in this mode (bf16x3: "
@@ -94,21 +60,7 @@ def main():
         lo, _, hi = part.partition("-")
         tiles += list(range(int(lo), int(hi or lo) + 1))
     dev = torch.device("cuda", 0)
-    torch.manual_seed(42)
-    from dfu_hip import nn as hnn
-    from dfu_hip.optim import FusedAdamW
-    model, fwd = bench.build(a.config, dev)
-    opt = FusedAdamW(model.parameters(), lr=1e-4, weight_decay=1e-4)
-    crit = hnn.CrossEntropyLoss(weight=torch.tensor([2.0, 2.0], device=dev))
-    rgb, th, y = bench.synthetic(a.batch, dev, 42)
-    from dfu_hip import functional as Fn
-    ops.gemm_record = []
-    opt.zero_grad()
-    with Fn.precision(a.precision):
-        crit(fwd(model, rgb, th), y).backward()
-    opt.step()
-    rec, ops.gemm_record = ops.gemm_record, None
-    torch.cuda.synchronize()
+    rec = _harness.record_step_gemms(_harness.fusion_step(a.config, a.batch), a.precision)
     uniq = {}
     for d, flops, _, refs, _ in rec:
         if a.only_x3_pairs and not d.x3_pairs:
@@ -117,9 +69,9 @@ def main():
             continue
         if a.only_wgrad and d.epilogue != L.EPI_F32_ACC:
             continue
-        uniq.setdefault(key(d), (d, flops, refs, []))[3].append(1)
+        uniq.setdefault(table_key(d), (d, flops, refs, []))[3].append(1)
     print(f"{len(rec)} launches, {len(uniq)} distinct GEMMs", flush=True)
-    ws = torch.empty(1 << 20, dtype=torch.uint8, device=dev)
+    ws = [torch.empty(1 << 20, dtype=torch.uint8, device=dev)]
     lines, t_auto_sum, t_best_sum = [], 0.0, 0.0
     dump = {}
     t0 = time.time()
@@ -127,7 +79,7 @@ def main():
         n = len(cnt)
         d = copy_desc(d0)
         d.tile, d.split_k = 0, 0
-        t_auto, ws = time_desc(d, a.iters, ws)
+        t_auto = time_desc(d, a.iters, ws)
         best = (t_auto, 0, 0)
         ktiles = (d0.K + 63) // 64
         cand = sorted(set(SPLITS) | set(range(1, 33))) if a.all_splits else SPLITS
@@ -137,7 +89,7 @@ def main():
                 d = copy_desc(d0)
                 d.tile, d.split_k = tile, sk
                 try:
-                    t, ws = time_desc(d, a.iters, ws)
+                    t = time_desc(d, a.iters, ws)
                 except L.DfuError:
                     break  # tile not instantiated for this combination
                 dump.setdefault(",".join(map(str, k)), {"n": n, "t": {}})["t"][f"{tile}/{sk}"] = t
@@ -145,7 +97,7 @@ def main():
                     best = (t, tile, sk)
         t_auto_sum += n * t_auto
         t_best_sum += n * min(best[0], t_auto)
-        name = (f"{OPND[d0.a_mode]}x{OPND[d0.b_mode]}->{EPI[d0.epilogue]}{'/P' if d0.x3_pairs else ''}{'/f16' if d0.operand_type == 1 else ''} "
+        name = (f"{gemm_label(d0, long=True)}{'/P' if d0.x3_pairs else ''}{'/f16' if d0.operand_type == 1 else ''} "
                 f"{d0.M}x{d0.N}x{d0.K} (x{n}/step)")
         print(f"{name:62s} auto {t_auto:8.1f} us  best {best[0]:8.1f} us tile {best[1]} "
               f"split {best[2]}  {flops / best[0] / 1e6:6.0f} TFLOP/s", flush=True)

@@ -8,20 +8,14 @@
 2. cProfile of eager steps with the backward on the calling thread: the callers of torch.empty /
    torch.empty_like / ops.gemm (which layer allocates and launches how often per step).
 """
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dfu-multimodal_amd")]
-import torch  # noqa: E402
+import _harness
+import torch
 
-import bench  # noqa: E402
-from dfu_hip import _lib as L  # noqa: E402
-from dfu_hip import functional as Fn  # noqa: E402
-from dfu_hip import nn as hnn  # noqa: E402
-from dfu_hip import ops  # noqa: E402
-from dfu_hip.optim import FusedAdamW  # noqa: E402
+from dfu_hip import functional as Fn
+from dfu_hip import ops
 
 
 def _host_us(fn, n=400):
@@ -72,20 +66,10 @@ def micro(dev):
         print(f"  {k:48s} {v:7.2f} us")
 
 
-def profile(dev, steps=5):
+def profile(steps=5):
     import cProfile
     import pstats
-    torch.manual_seed(42)
-    model, fwd = bench.build("fusion", dev)
-    opt = FusedAdamW(model.parameters(), lr=1e-4, weight_decay=1e-4)
-    crit = hnn.CrossEntropyLoss(weight=torch.tensor([2.0, 2.0], device=dev))
-    rgb, th, y = bench.synthetic(64, dev, seed=42)
-
-    def step():
-        opt.zero_grad()
-        crit(fwd(model, rgb, th), y).backward()
-        Fn.join_grad_streams()
-        opt.step()
+    step = _harness.fusion_step().step
     for _ in range(3):
         step()
     torch.cuda.synchronize()
@@ -113,7 +97,7 @@ def main():
     print("launch micro-costs (host us per call):")
     micro(dev)
     if "--micro" not in sys.argv:
-        profile(dev)
+        profile()
 
 
 if __name__ == "__main__":

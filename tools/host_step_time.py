@@ -6,17 +6,12 @@ the GPU time of the step, to see whether the device waits for the host at the st
 """
 import argparse
 import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dfu-multimodal_amd")]
-import torch  # noqa: E402
+import _harness
+import torch
 
-import bench  # noqa: E402
-from dfu_hip import functional as Fn  # noqa: E402
-from dfu_hip import nn as hnn  # noqa: E402
-from dfu_hip.optim import FusedAdamW  # noqa: E402
+from dfu_hip import functional as Fn
 
 
 def main():
@@ -27,7 +22,6 @@ def main():
     ap.add_argument("--precision", default="parity")
     ap.add_argument("--pin", action="store_true", help="pin the process to four cores")
     a = ap.parse_args()
-    Fn.set_precision(a.precision)
     if a.pin and hasattr(os, "sched_setaffinity"):
         # four fixed cores (the calling thread, autograd's device thread, the runtime's): the
         # box's scheduler otherwise moves the process between cores of different speed mid-run
@@ -35,13 +29,9 @@ def main():
         os.sched_setaffinity(0, cores)
         print("pinned to cores", cores)
     if a.profile:
-        return profile()
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(42)
-    model, fwd = bench.build("fusion", dev)
-    opt = FusedAdamW(model.parameters(), lr=1e-4, weight_decay=1e-4)
-    crit = hnn.CrossEntropyLoss(weight=torch.tensor([2.0, 2.0], device=dev))
-    rgb, th, y = bench.synthetic(a.batch, dev, seed=42)
+        return profile(_harness.fusion_step(precision=a.precision).step)
+    model, fwd, opt, crit, (rgb, th, y), _ = _harness.fusion_step(batch=a.batch,
+                                                                  precision=a.precision)
     phases = ["zero_grad", "forward", "loss", "backward", "join", "opt.step"]
     acc = {k: [] for k in phases}
     gpu = []
@@ -78,24 +68,10 @@ def main():
     print(f"host fastest step {min(tot):.3f} ms, lower quartile {sorted(tot)[len(tot) // 4]:.3f} ms")
 
 
-
-
-def profile(steps=5):
+def profile(step, steps=5):
     """cProfile of the host side of `steps` eager steps (after warm-up): top functions."""
     import cProfile
     import pstats
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(42)
-    model, fwd = bench.build("fusion", dev)
-    opt = FusedAdamW(model.parameters(), lr=1e-4, weight_decay=1e-4)
-    crit = hnn.CrossEntropyLoss(weight=torch.tensor([2.0, 2.0], device=dev))
-    rgb, th, y = bench.synthetic(64, dev, seed=42)
-
-    def step():
-        opt.zero_grad()
-        crit(fwd(model, rgb, th), y).backward()
-        Fn.join_grad_streams()
-        opt.step()
     for _ in range(3):
         step()
     torch.cuda.synchronize()

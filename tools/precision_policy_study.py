@@ -13,18 +13,17 @@ for every policy that passes on all seeds (and the pure modes).
 import argparse
 import json
 import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dfu-multimodal_amd")]
-import torch  # noqa: E402
+import _harness
+import torch
 
-from dfu_hip import functional as Fn  # noqa: E402
-from models import precision as P  # noqa: E402
-from models.fusion import MultimodalFusionModel  # noqa: E402
-from oracle import torch_ref as R  # noqa: E402
+from dfu_hip import functional as Fn
+from models import precision as P
+from models.fusion import MultimodalFusionModel
+from oracle import torch_ref as R
 
+ROOT = _harness.ROOT
 RES_SUFFIX = (0, 1, 2, 3, 4, 5, 6, 7, 9, 13, 16)
 VIT_SUFFIX = (0, 1, 2, 3, 4, 5, 6, 8, 12)
 
@@ -80,34 +79,14 @@ def main():
             res["cases"].setdefault(name, []).append(d)
             print(f"  {name:24s}: {d:.3e}", flush=True)
         del ref
-    from dfu_hip import nn as hnn
-    from dfu_hip.optim import FusedAdamW
     passing = [k for k, ds in res["cases"].items() if max(ds) <= a.bar]
     print("passing:", passing, flush=True)
     model = hip
-    opt = FusedAdamW(model.parameters(), lr=1e-4, weight_decay=1e-4)
-    crit = hnn.CrossEntropyLoss(weight=torch.tensor([2.0, 2.0], device=dev))
     g = torch.Generator(device=dev).manual_seed(0)
     rgb = torch.randn(a.batch, 3, 224, 224, device=dev, generator=g)
     th = torch.randn(a.batch, 3, 224, 224, device=dev, generator=g)
     y = torch.randint(0, 2, (a.batch,), device=dev, generator=g)
-
-    def step():
-        opt.zero_grad()
-        crit(model(rgb, th), y).backward()
-        opt.step()
-
-    def timeit():
-        for _ in range(4):
-            step()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.time_steps):
-            step()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / a.time_steps
+    step = _harness.fusion_step(model=model, inputs=(rgb, th, y)).step
 
     res["step_ms"] = {}
     pols = policies(model, a.grid)
@@ -118,7 +97,7 @@ def main():
             P.apply_policy(model, pols[k])
             mode = "mixed"
         with Fn.precision(mode):
-            ms = timeit()
+            ms = _harness.time_us(step, a.time_steps, 4) / 1e3
         res["step_ms"][k] = round(ms, 3)
         print(f"step {k:24s}: {ms:.3f} ms", flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

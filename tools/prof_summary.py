@@ -16,6 +16,8 @@ import csv
 import json
 import re
 
+import _harness
+
 CATS = [
     ("GEMM (MFMA template)", r"gemm_kernel<|gemm_p8<|gemm_ps<"),
     ("GEMM split-K reduce", r"k_splitk_reduce"),
@@ -52,10 +54,8 @@ def cat(name):
     return "other"
 
 
-OPND = ["KM", "MN", "CONV_FWD", "CONV_DGRAD", "CONV_DGRAD_W", "CONV_WGRAD_X"]
-EPI = ["BF16", "BF16_RELU", "BF16_GELU", "F32", "F32_RESID", "BF16_DGELU", "BF16_ADD", "F32_ACC",
-       "F32_ACC_CONVW", "BF16_STATS", "PATCH", "F32_STATS", "BF16_DSTATS", "X3_GELU", "F16_DUAL",
-       "F16_GELU"]
+OPND = [long for _, long in _harness.OPND_NAMES]
+EPI = [long for _, long in _harness.EPI_NAMES]
 
 
 def gemm_label(name):

@@ -10,20 +10,11 @@ it leaves idle); this measures the step instead.
       [--config rgb]
 """
 import argparse
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dfu-multimodal_amd")]
-import torch  # noqa: E402
+import _harness
 
-import bench  # noqa: E402
-from dfu_hip import _lib as L  # noqa: E402
-from dfu_hip import functional as Fn  # noqa: E402
-from dfu_hip import nn as hnn  # noqa: E402
-from dfu_hip._lib import (EPI_BF16, EPI_BF16_DGELU, EPI_F16_GELU, EPI_F32_ACC,  # noqa: E402
-                          EPI_F32_RESID)
-from dfu_hip.optim import FusedAdamW  # noqa: E402
+from dfu_hip import _lib as L
+from dfu_hip._lib import EPI_BF16, EPI_BF16_DGELU, EPI_F16_GELU, EPI_F32_ACC, EPI_F32_RESID
 
 # variant -> C-ABI symbols skipped, or ("gemm", predicate on the descriptor)
 VARIANTS = {
@@ -83,31 +74,12 @@ def main():
     ap.add_argument("--variants", default=",".join(VARIANTS))
     ap.add_argument("--config", default="fusion", help="fusion | rgb | thermal (bench.build)")
     a = ap.parse_args()
-    dev = torch.device("cuda", 0)
     proxy = _Proxy(L.load())
     L._lib = proxy  # every L.load() / ops.lib() from here on returns the proxy
-    torch.manual_seed(42)
-    model, fwd = bench.build(a.config, dev)
-    opt = FusedAdamW(model.parameters(), lr=1e-4, weight_decay=1e-4)
-    crit = hnn.CrossEntropyLoss(weight=torch.tensor([2.0, 2.0], device=dev))
-    rgb, th, y = bench.synthetic(64, dev, seed=42)
-
-    def step():
-        opt.zero_grad()
-        loss = crit(fwd(model, rgb, th), y)
-        loss.backward()
-        Fn.join_grad_streams()
-        opt.step()
+    step = _harness.fusion_step(a.config).step
 
     def timed(n):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            step()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n
+        return _harness.time_us(step, n, 0) / 1e3
 
     for _ in range(5):
         step()

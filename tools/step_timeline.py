@@ -6,18 +6,12 @@ event); the host enqueued it at h[i].  g[i] - h[i] is how far the device runs be
 where it is small the device has caught up and waits for the host's enqueue.
   python tools/step_timeline.py [--steps 8] [--precision parity]"""
 import argparse
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "dfu-multimodal_amd")]
-import torch  # noqa: E402
+import _harness
+import torch
 
-import bench  # noqa: E402
-from dfu_hip import functional as Fn  # noqa: E402
-from dfu_hip import nn as hnn  # noqa: E402
-from dfu_hip.optim import FusedAdamW  # noqa: E402
+from dfu_hip import functional as Fn
 
 
 def main():
@@ -25,14 +19,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--precision", default=None)
     a = ap.parse_args()
-    if a.precision:
-        Fn.set_precision(a.precision)
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(42)
-    model, fwd = bench.build("fusion", dev)
-    opt = FusedAdamW(model.parameters(), lr=1e-4, weight_decay=1e-4)
-    crit = hnn.CrossEntropyLoss(weight=torch.tensor([2.0, 2.0], device=dev))
-    rgb, th, y = bench.synthetic(64, dev, seed=42)
+    model, fwd, opt, crit, (rgb, th, y), _ = _harness.fusion_step(precision=a.precision)
     names = []
     evs, hs = [], []
     # per-encoder end-of-backward events (recorded on the stream each backward runs on)
