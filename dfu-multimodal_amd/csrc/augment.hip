@@ -14,6 +14,13 @@
 //                                 normalisation in fp32 with IEEE division -> fp32 NCHW
 //   ImageEnhance.Contrast needs the mean grey level of the image it is applied to: one block
 //   per image reduces it first (k_augment_stats).
+//   GaussianBlur(3, sigma)        the thermal-only script's last random op
+//                                 (notebooks/train_thermal_only.py:103-112), between RandomAffine
+//                                 and ToTensor: torchvision F.gaussian_blur on the u8 image,
+//                                 reflect pad 1, nine fp32 taps, round half to even
+//                                 (k_augment_blur in place of k_augment_apply: an LDS tile of
+//                                 pre-blur pixels with halo; dfu_augment_blur).  Restated from
+//                                 torchvision's source, parity unpinned (dfu_hip.h).
 // Random parameters are drawn on the host (data/gpu_transforms.py) and arrive per image as
 // dfu_aug_params; all arithmetic here is integer except the blends and the normalisation.
 // Test-time augmentation (notebooks/test_time_augmentation.py:145-167) uses the same two kernels
@@ -240,6 +247,105 @@ int launch_augment(const uint8_t* img, const dfu_aug_params* params, const int32
   return DFU_OK;
 }
 
+// GaussianBlur(kernel_size=3) after the ops above (the thermal-only train transform).  One block
+// produces a kBlurTW x kBlurTH tile: it first stages the tile's pre-blur pixels (what
+// k_augment_apply computes at that position) plus a 1-pixel halo in LDS, u8 x 3 packed in a
+// dword, so the inverse maps and the blends run once per pixel and not once per tap.  The halo
+// reflects about the edge of the augmented image (-1 -> 1, W -> W - 2) before the inverse
+// chain, so rotation / affine fill is blurred into its neighbours.  A 32-lane half reads 32
+// consecutive dwords of one LDS row for every tap and the staging stores are consecutive too:
+// no bank conflicts at the unpadded row stride.
+constexpr int kBlurTW = 32, kBlurTH = 8;
+constexpr int kBlurLW = kBlurTW + 2, kBlurLH = kBlurTH + 2;
+
+template <int ORDER>
+DFU_DEV Px augmented(const uint8_t* im, const dfu_aug_params& P, int src, int W, int H, int mean,
+                     int x, int y) {
+  Px p = {{0, 0, 0}};
+  if (src >= 0 && (!P.affine || affine_src(P.aff, x, y, W, H, x, y)))
+    p = colour(rotated<ORDER>(im, P, W, H, x, y), P, P.n_ops, mean);
+  return p;
+}
+
+// blur_k: fp32 [n_out][3], the 1-D weights of each output; k[1] == 0 means no blur, and that
+// block takes k_augment_apply's per-pixel path (the branch is uniform over the block).
+template <int ORDER>
+__global__ void __launch_bounds__(kBlurTW * kBlurTH)
+    k_augment_blur(const uint8_t* __restrict__ img, const dfu_aug_params* __restrict__ params,
+                   const int32_t* __restrict__ view_src, const float* __restrict__ blur_k,
+                   int n_images, const int32_t* __restrict__ means, int H, int W, int tiles_x,
+                   float m0, float m1, float m2, float s0, float s1, float s2,
+                   float* __restrict__ out) {
+  __shared__ uint32_t tile[kBlurLH * kBlurLW];
+  const dfu_aug_params P = params[blockIdx.y];
+  const int src = view_image(view_src, blockIdx.y, n_images);
+  const uint8_t* im = img + (int64_t)(src < 0 ? 0 : src) * H * W * 3;
+  const int n = H * W;
+  const int mean = contrast_slot(P) >= 0 ? (int)((2 * (int64_t)means[blockIdx.y] + n) / (2 * (int64_t)n)) : 0;
+  const float* bk = blur_k + 3 * (int64_t)blockIdx.y;
+  const float k0 = bk[0], k1 = bk[1], k2 = bk[2];
+  const int x0 = (int)(blockIdx.x % tiles_x) * kBlurTW, y0 = (int)(blockIdx.x / tiles_x) * kBlurTH;
+  const int tx = threadIdx.x % kBlurTW, ty = threadIdx.x / kBlurTW;
+  const int x = x0 + tx, y = y0 + ty;
+  const bool inside = x < W && y < H;
+  Px p = {{0, 0, 0}};
+  if (k1 == 0.f) {
+    if (inside) p = augmented<ORDER>(im, P, src, W, H, mean, x, y);
+  } else {
+    for (int i = threadIdx.x; i < kBlurLH * kBlurLW; i += kBlurTW * kBlurTH) {
+      int hx = x0 - 1 + i % kBlurLW, hy = y0 - 1 + i / kBlurLW;
+      uint32_t v = 0;
+      if (hx <= W && hy <= H) {  // past that no output of this tile reads it
+        hx = hx < 0 ? 1 : (hx == W ? W - 2 : hx);
+        hy = hy < 0 ? 1 : (hy == H ? H - 2 : hy);
+        const Px q = augmented<ORDER>(im, P, src, W, H, mean, hx, hy);
+        v = (uint32_t)q.c[0] | (uint32_t)q.c[1] << 8 | (uint32_t)q.c[2] << 16;
+      }
+      tile[i] = v;
+    }
+    __syncthreads();
+    if (inside) {
+      // torchvision's 2-D kernel: fp32(k[j] * k[i]); the nine taps row-major, sequential adds
+      const float kk[3] = {k0, k1, k2};
+      float acc[3] = {0.f, 0.f, 0.f};
+      for (int j = 0; j < 3; ++j)
+        for (int i = 0; i < 3; ++i) {
+          const float w = kk[j] * kk[i];
+          const uint32_t v = tile[(ty + j) * kBlurLW + tx + i];
+          acc[0] = acc[0] + w * (float)(v & 255u);
+          acc[1] = acc[1] + w * (float)(v >> 8 & 255u);
+          acc[2] = acc[2] + w * (float)(v >> 16 & 255u);
+        }
+      for (int c = 0; c < 3; ++c) p.c[c] = (int)rintf(acc[c]);  // torch.round: half to even
+    }
+  }
+  if (inside) {
+    float* o = out + (int64_t)blockIdx.y * 3 * n;
+    const int i = y * W + x;
+    o[i] = ((float)p.c[0] / 255.f - m0) / s0;
+    o[n + i] = ((float)p.c[1] / 255.f - m1) / s1;
+    o[2 * n + i] = ((float)p.c[2] / 255.f - m2) / s2;
+  }
+}
+
+template <int ORDER>
+int launch_blur(const uint8_t* img, const dfu_aug_params* params, const int32_t* view_src,
+                const float* blur_k, int n_images, int n_out, int H, int W, const float* mean3,
+                const float* std3, int32_t* contrast_means, float* out, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(contrast_means, 0, sizeof(int32_t) * n_out, stream);
+  DFU_CHECK_ARG(e == hipSuccess, "augment: memset: %s", hipGetErrorString(e));
+  hipLaunchKernelGGL(k_augment_stats<ORDER>, dim3(kStatBlocks, n_out), dim3(256), 0, stream, img,
+                     params, view_src, n_images, H, W, contrast_means);
+  DFU_LAUNCH_CHECK();
+  const int tiles_x = (W + kBlurTW - 1) / kBlurTW, tiles_y = (H + kBlurTH - 1) / kBlurTH;
+  hipLaunchKernelGGL(k_augment_blur<ORDER>, dim3(tiles_x * tiles_y, n_out),
+                     dim3(kBlurTW * kBlurTH), 0, stream, img, params, view_src, blur_k, n_images,
+                     contrast_means, H, W, tiles_x, mean3[0], mean3[1], mean3[2], std3[0],
+                     std3[1], std3[2], out);
+  DFU_LAUNCH_CHECK();
+  return DFU_OK;
+}
+
 }  // namespace
 
 // PIL Resample.c precompute_coeffs + normalize_coeffs_8bpc for the bilinear filter (support 1):
@@ -328,4 +434,24 @@ extern "C" int dfu_augment_views(const uint8_t* img, int32_t n_images,
   return launch_augment<DFU_AUG_ORDER_FLIP_ROTATE>(img, params, view_src, n_images, n_views, H, W,
                                                    mean3, std3, contrast_means, out,
                                                    (hipStream_t)stream);
+}
+
+extern "C" int dfu_augment_blur(const uint8_t* img, int32_t n_images, const dfu_aug_params* params,
+                                const int32_t* view_src, const float* blur_k, int32_t n_views,
+                                int32_t order, int32_t H, int32_t W, const float* mean3,
+                                const float* std3, int32_t* contrast_means, float* out,
+                                void* stream) {
+  DFU_CHECK_ARG(img && params && blur_k && mean3 && std3 && contrast_means && out &&
+                    n_images > 0 && n_views > 0 && n_views <= 65535 && H >= 2 && W >= 2 &&
+                    (int64_t)H * W * 255 < (1ll << 31),
+                "dfu_augment_blur: bad args");
+  DFU_CHECK_ARG(order == DFU_AUG_ORDER_FLIP_ROTATE || order == DFU_AUG_ORDER_ROTATE_FLIP,
+                "dfu_augment_blur: order %d", order);
+  if (order == DFU_AUG_ORDER_ROTATE_FLIP)
+    return launch_blur<DFU_AUG_ORDER_ROTATE_FLIP>(img, params, view_src, blur_k, n_images,
+                                                  n_views, H, W, mean3, std3, contrast_means, out,
+                                                  (hipStream_t)stream);
+  return launch_blur<DFU_AUG_ORDER_FLIP_ROTATE>(img, params, view_src, blur_k, n_images, n_views,
+                                                H, W, mean3, std3, contrast_means, out,
+                                                (hipStream_t)stream);
 }

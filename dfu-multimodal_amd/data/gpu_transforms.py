@@ -14,8 +14,16 @@ requirements, not installed here): RandomHorizontalFlip / RandomVerticalFlip
 `torch.rand(1) < p`; RandomRotation `uniform_(-deg, deg)`; RandomApply `p < torch.rand(1)`
 skips; ColorJitter `randperm(4)` then brightness, contrast, saturation factors
 `uniform_(1 - 0.3, 1 + 0.3)`; RandomAffine angle, tx, ty (`int(round(uniform_(-0.1 W, 0.1 W)))`),
-scale.  The pixel arithmetic given those parameters is pinned against PIL itself
-(tests/test_augment_gpu.py); the draw order is "parity unpinned" (torchvision absent).
+scale; RandomApply coin, then GaussianBlur sigma `uniform_(0.1, 0.5)`.  The pixel arithmetic
+given those parameters is pinned against PIL itself (tests/test_augment_gpu.py); the draw order
+is "parity unpinned" (torchvision absent).
+
+The thermal-only script's train transform (train_thermal_only.py:103-112,
+`thermal_only_train_transform`) ends in RandomApply([GaussianBlur(3, (0.1, 0.5))]).  torchvision
+blurs a PIL image as a tensor (F.gaussian_blur: fp32 conv2d after a reflect pad, torch.round
+back to uint8), not through PIL, so that arithmetic is restated from its source, parity
+unpinned (include/dfu_hip.h, dfu_augment_blur; tests/test_blur_gpu.py pins it against an fp64
+restatement up to rounding ties).
 
 Test-time augmentation (notebooks/test_time_augmentation.py:145-167): `rgb_tta_transform` /
 `thermal_tta_transform` put the rotation before the flips (TransformSpec.order) and use a bare
@@ -25,7 +33,7 @@ image from one decode, one copy and one resize (dfu_augment_views; tests/test_tt
 import ctypes
 import math
 from concurrent.futures import ThreadPoolExecutor
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from functools import lru_cache
 
 import numpy as np
@@ -63,10 +71,19 @@ class TransformSpec:
     std: tuple = IMAGENET_STD
     order: str = "flip_rotate"                # flips then rotation (the train scripts), or
                                               # "rotate_flip" (test_time_augmentation.py)
+    blur: tuple = None                        # GaussianBlur sigma range (sigma_min, sigma_max),
+                                              # after the affine
+    blur_p: float = 0.0                       # RandomApply's p; None = a bare GaussianBlur
+    blur_kernel: int = 3                      # GaussianBlur kernel_size: only 3 is implemented
+
+    def __post_init__(self):
+        if self.blur_kernel != 3:
+            raise NotImplementedError(f"GaussianBlur kernel_size {self.blur_kernel}: only 3")
 
     @property
     def random(self):
-        return bool(self.hflip_p or self.vflip_p or self.rotation or self.jitter or self.affine)
+        return bool(self.hflip_p or self.vflip_p or self.rotation or self.jitter or self.affine
+                    or self.blur)
 
 
 # train_multimodal_fusion.py:172-205
@@ -78,6 +95,10 @@ thermal_train_transform = TransformSpec(hflip_p=0.5, vflip_p=0.5, rotation=30,
                                         affine=(20, (0.1, 0.1), (0.8, 1.2)), affine_p=AUG_PROB,
                                         mean=THERMAL_MEAN, std=THERMAL_STD)
 thermal_val_test_transform = TransformSpec(mean=THERMAL_MEAN, std=THERMAL_STD)
+# train_thermal_only.py:103-112: the thermal train transform, then
+# RandomApply([GaussianBlur(kernel_size=3, sigma=(0.1, 0.5))], p=AUG_PROB)
+thermal_only_train_transform = replace(thermal_train_transform, blur=(0.1, 0.5),
+                                       blur_p=AUG_PROB)
 # test_time_augmentation.py:145-167 get_light_augmentation_transforms: Resize, RandomRotation(15),
 # the two flips, a bare RandomAffine(10, translate=(0.05, 0.05)), ToTensor, Normalize
 rgb_tta_transform = TransformSpec(hflip_p=0.5, vflip_p=0.5, rotation=15,
@@ -98,6 +119,7 @@ class AugParams:
     angle: float = 0.0                        # RandomRotation
     ops: list = field(default_factory=list)   # [(op, factor)] ColorJitter, in applied order
     affine: tuple = None                      # (angle, (tx, ty), scale, (shear_x, shear_y))
+    blur: float = None                        # GaussianBlur sigma; None = not applied
 
 
 def _uniform(a, b, g):
@@ -134,7 +156,32 @@ def sample_params(spec, generator=None):
         ty = int(round(_uniform(-max_dy, max_dy, g)))
         scale = _uniform(*scale_range, g) if scale_range is not None else 1.0
         p.affine = (angle, (tx, ty), scale, (0.0, 0.0))
+    if spec.blur is not None and (spec.blur_p is None
+                                  or not (spec.blur_p < torch.rand(1, generator=g))):
+        p.blur = _uniform(float(spec.blur[0]), float(spec.blur[1]), g)
     return p
+
+
+def blur_weight_rows(sigmas):
+    """torchvision _get_gaussian_kernel1d(3, sigma) for every sigma of a batch: the three fp32
+    weights of GaussianBlur's separable kernel by the same torch ops (restated), fp32 [n][3],
+    with a zero row (no blur) for None.  One set of torch calls on an [n, 3] tensor per batch,
+    not one per sample (3 ms per batch of 64, EXPERIMENTS.md); each row has the bits the ops
+    give for that sigma alone (tests/test_blur_cpu.py).  The 2-D weight of tap (j, i) is
+    fp32(k[j] * k[i]), formed in the kernel."""
+    rows = np.zeros((len(sigmas), 3), np.float32)
+    idx = [i for i, s in enumerate(sigmas) if s is not None]
+    if idx:
+        sig = torch.tensor([sigmas[i] for i in idx], dtype=torch.float64).float()
+        x = torch.linspace(-1, 1, steps=3)
+        pdf = torch.exp(-0.5 * (x[None, :] / sig[:, None]).pow(2))
+        rows[idx] = (pdf / pdf.sum(1, keepdim=True)).numpy()
+    return rows
+
+
+def blur_weights(sigma):
+    """The three fp32 weights of one sigma."""
+    return blur_weight_rows([sigma])[0]
 
 
 # ------------------------------------------------------------------ inverse maps (host)
@@ -237,6 +284,8 @@ class GpuPreprocessor:
     def __init__(self, spec, device="cuda"):
         self.spec = spec
         self.device = torch.device(device)
+        if spec.blur is not None and min(spec.size) < 2:
+            raise ValueError(f"GaussianBlur reflects about the edge: size {spec.size} < 2 x 2")
         self._mean = (ctypes.c_float * 3)(*spec.mean)
         self._std = (ctypes.c_float * 3)(*spec.std)
 
@@ -282,9 +331,14 @@ class GpuPreprocessor:
         # with views, each record's source image follows the records: view_src int32 [n * K]
         view_src = (np.repeat(np.arange(n, dtype=np.int32), views) if views is not None
                     else np.empty(0, np.int32))
-        # one staging buffer: [descs | params, view_src | taps | pixels], 256-byte aligned sections
+        # with a blur, each record's 1-D weights: blur_k fp32 [nv][3], zeros = not blurred
+        blur_k = (blur_weight_rows([p.blur for p in params]) if spec.blur is not None
+                  else np.empty(0, np.float32))
+        # one staging buffer: [descs | params, view_src | blur_k | taps | pixels], 256-byte aligned
+        # sections (no blur_k section without spec.blur)
         o_par = _align(desc.nbytes)
-        o_coef = o_par + _align(rec.nbytes + view_src.nbytes)
+        o_blur = o_par + _align(rec.nbytes + view_src.nbytes)
+        o_coef = o_blur + _align(blur_k.nbytes)
         o_src = o_coef + _align(coef_len * 4)
         total = o_src + src_len + 4  # the resize reads whole dwords of the last row
         stage = torch.empty(total, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
@@ -292,6 +346,7 @@ class GpuPreprocessor:
         buf[:desc.nbytes] = desc.view(np.uint8)
         buf[o_par:o_par + rec.nbytes] = rec.view(np.uint8)
         buf[o_par + rec.nbytes:o_par + rec.nbytes + view_src.nbytes] = view_src.view(np.uint8)
+        buf[o_blur:o_blur + blur_k.nbytes] = blur_k.reshape(-1).view(np.uint8)
         cv = buf[o_coef:o_coef + coef_len * 4].view(np.int32)
         at = 0
         for t in taps:
@@ -303,11 +358,13 @@ class GpuPreprocessor:
             buf[at:at + im.size] = im.ravel()
             at += im.size
         return _Staged(stage.to(self.device, non_blocking=True), n, o_par, o_coef, o_src,
-                       tmp_len, views, o_par + rec.nbytes)
+                       tmp_len, views, o_par + rec.nbytes,
+                       o_blur if spec.blur is not None else None)
 
     def run(self, st):
         """Device side: resize + augment + normalise a staged batch (4 launches); a batch staged
-        with views gives [n * K, 3, H, W], sample-major (dfu_augment_views)."""
+        with views gives [n * K, 3, H, W], sample-major (dfu_augment_views).  A spec with a blur
+        goes through dfu_augment_blur instead, with or without views."""
         OH, OW = self.spec.size
         if st.n == 0:
             return torch.empty((0, 3, OH, OW), dtype=torch.float32, device=self.device)
@@ -321,6 +378,19 @@ class GpuPreprocessor:
                                    ctypes.c_void_p(tmp.data_ptr()),
                                    ctypes.c_void_p(resized.data_ptr()), stream),
               "dfu_resize_batch")
+        if self.spec.blur is not None:
+            nv = st.n * (st.views or 1)
+            out = torch.empty((nv, 3, OH, OW), dtype=torch.float32, device=self.device)
+            means = torch.empty(nv, dtype=torch.int32, device=self.device)
+            view_src = ctypes.c_void_p(base + st.o_view) if st.views is not None else None
+            check(lib.dfu_augment_blur(ctypes.c_void_p(resized.data_ptr()), st.n,
+                                       ctypes.c_void_p(base + st.o_par), view_src,
+                                       ctypes.c_void_p(base + st.o_blur), nv,
+                                       ORDERS[self.spec.order], OH, OW, self._mean, self._std,
+                                       ctypes.c_void_p(means.data_ptr()),
+                                       ctypes.c_void_p(out.data_ptr()), stream),
+                  "dfu_augment_blur")
+            return out
         if st.views is not None:
             nv = st.n * st.views
             out = torch.empty((nv, 3, OH, OW), dtype=torch.float32, device=self.device)
@@ -353,6 +423,7 @@ class _Staged:
     tmp_len: int
     views: int = None      # K parameter records per image (dfu_augment_views), None: one each
     o_view: int = 0        # view_src int32 [n * K]
+    o_blur: int = None     # blur_k fp32 [n * K][3] (dfu_augment_blur), None: a spec without blur
 
 
 def decode_rgb(path):
@@ -450,10 +521,11 @@ class GpuImageLoader:
     RGBDataset, train_rgb_only.py:181-197; ThermalDataset): yields (images, labels) already on
     the GPU, fp32 NCHW, through the same decode-ahead threads and HIP transform kernels as
     GpuPairLoader.  `spec` defaults to the RGB train / val-test transform of
-    train_rgb_only.py:102-118 (the fusion script's RGB transforms, identical); the thermal-only
-    script's train transform adds a GaussianBlur this pipeline does not implement, so a thermal
-    loader takes `thermal_val_test_transform` (or a spec without blur).  views=K > 1: [B * K, 3,
-    H, W] images, sample-major, and [B] labels, as GpuPairLoader."""
+    train_rgb_only.py:102-118 (the fusion script's RGB transforms, identical).  The thermal-only
+    script's loaders (train_thermal_only.py:103-118) are GpuImageLoader(ds, bs, train=True,
+    spec=thermal_only_train_transform), whose train transform ends in a GaussianBlur, and
+    spec=thermal_val_test_transform.  views=K > 1: [B * K, 3, H, W] images, sample-major, and
+    [B] labels, as GpuPairLoader."""
 
     def __init__(self, dataset, batch_size, sampler=None, shuffle=False, train=False,
                  spec=None, device="cuda", num_threads=4, generator=None, drop_last=False,

@@ -646,6 +646,25 @@ int dfu_resize_batch(const uint8_t* src, const dfu_resize_desc* descs, const int
 int dfu_augment_normalize(const uint8_t* img, const dfu_aug_params* params, int32_t n,
                           int32_t H, int32_t W, const float* mean3, const float* std3,
                           int32_t* contrast_means, float* out, void* stream);
+/* dfu_augment_views (below) with the thermal-only script's GaussianBlur(kernel_size=3, sigma)
+ * (notebooks/train_thermal_only.py:103-112) between RandomAffine and ToTensor.  view_src NULL:
+ * view v reads image v, as dfu_augment_normalize.  blur_k: device fp32 [n_views][3], the 1-D
+ * weights of each view; a row with k[1] == 0 means no blur, and that view's output equals
+ * dfu_augment_normalize's / dfu_augment_views', bitwise (a real blur has k[1] > 0).
+ * Arithmetic (torchvision 0.17 F.gaussian_blur on a PIL image, restated from its source:
+ * torchvision is not installed, parity unpinned):
+ *   weights, on the host in fp32 torch ops: x = linspace(-1, 1, 3), pdf = exp(-0.5 (x / sigma)^2),
+ *     k = pdf / pdf.sum(); one sigma for both axes; the weight of tap (j, i) is fp32(k[j] * k[i]),
+ *     one rounding;
+ *   per channel of the augmented u8 image (fill included): u8 -> fp32, reflect pad by 1
+ *     (index -1 -> 1, W -> W - 2), the nine products added row-major by sequential fp32 adds
+ *     without FMA contraction, round half to even, -> u8; then ((float)p / 255 - mean) / std.
+ * The contrast mean is of the pre-blur image.  H >= 2 and W >= 2 (the reflection needs two
+ * pixels), n_views <= 65535; otherwise DFU_E_INVALID. */
+int dfu_augment_blur(const uint8_t* img, int32_t n_images, const dfu_aug_params* params,
+                     const int32_t* view_src, const float* blur_k, int32_t n_views,
+                     int32_t order, int32_t H, int32_t W, const float* mean3,
+                     const float* std3, int32_t* contrast_means, float* out, void* stream);
 
 /* ------------------------------------------------------- test-time augmentation ---- */
 /* The robustness evaluation of notebooks/test_time_augmentation.py: K random views of every

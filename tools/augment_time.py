@@ -1,6 +1,8 @@
 """Time the GPU input pipeline on a batch of decoded images: the whole GpuPreprocessor call (host
 staging + one H2D copy + the two HIP kernels) on a host clock, and the reference's per-sample
-PIL/torch transform on one host core for comparison."""
+PIL/torch transform on one host core for comparison.  --spec picks the train transform: rgb (the
+default), thermal, or thermal_only (the thermal one plus the GaussianBlur of
+train_thermal_only.py; the host reference has no blur, so its figure is of the other ops)."""
 import argparse
 import os
 import sys
@@ -12,6 +14,9 @@ import torch
 
 from data import gpu_transforms as GT
 
+SPECS = {"rgb": GT.rgb_train_transform, "thermal": GT.thermal_train_transform,
+         "thermal_only": GT.thermal_only_train_transform}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -19,11 +24,12 @@ def main():
     ap.add_argument("--h", type=int, default=480)
     ap.add_argument("--w", type=int, default=640)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--spec", choices=sorted(SPECS), default="rgb")
     a = ap.parse_args()
 
     rng = np.random.default_rng(0)
     imgs = [rng.integers(0, 256, (a.h, a.w, 3), dtype=np.uint8) for _ in range(a.batch)]
-    spec = GT.rgb_train_transform
+    spec = SPECS[a.spec]
     g = torch.Generator().manual_seed(0)
     params = [GT.sample_params(spec, g) for _ in imgs]
     pre = GT.GpuPreprocessor(spec)
@@ -35,7 +41,8 @@ def main():
         pre(imgs, params)
     torch.cuda.synchronize()
     full = (time.perf_counter() - t0) / a.iters
-    print(f"GpuPreprocessor batch {a.batch} of {a.h}x{a.w}: {full * 1e3:.2f} ms/batch "
+    what = "" if a.spec == "rgb" else f" [{a.spec}]"
+    print(f"GpuPreprocessor{what} batch {a.batch} of {a.h}x{a.w}: {full * 1e3:.2f} ms/batch "
           f"({a.batch / full:.0f} img/s incl. host staging + H2D)")
     sys.path.insert(0, os.path.join(_harness.ROOT, "oracle"))
     import transforms_ref as TR
