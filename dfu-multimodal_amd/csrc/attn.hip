@@ -399,8 +399,9 @@ __global__ __launch_bounds__(512) void k_attn_bwd_fused(const bf16_t* __restrict
     d += __shfl_xor(d, 2, 64);
     d += __shfl_xor(d, 4, 64);
     // padding queries get LSE = +inf: every probability of theirs is exp2(-inf) = 0, so no
-    // element needs a query mask below; padding keys need none either (their K, V rows are 0,
-    // so they add nothing to dQ, and their own dK / dV rows are never stored)
+    // element needs a query mask below.  Padding keys: the dQ pass zeroes their dS (their K rows
+    // are 0, but their dS can be inf); in the dK/dV pass a padding key only feeds its own dK / dV
+    // rows, which are never stored
     if (chunk == 0) {
       Es[row] = row < N ? d : 0.f;
       Ls[row] = row < N ? lse[(int64_t)bh * NPAD + row] * LOG2E : INFINITY;
@@ -436,6 +437,14 @@ __global__ __launch_bounds__(512) void k_attn_bwd_fused(const bf16_t* __restrict
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) st[r] = fast_exp2(fmaf(st[r], c, -lq)) * (dp[r] - dsum);
+        // padding keys of a partly filled tile (the last two tiles only, as in the forward): their
+        // score is 0, so their "probability" exp2(-lq) is +inf for lse < -88.7 and dS = inf * (0 -
+        // delta) would reach the real dQ rows as inf * 0 = NaN through the zero K rows
+        if (t >= KT - 2) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (16 * t + 4 * g + r >= N) st[r] = 0.f;
+        }
         s[t] = st;
       }
       f32x4 acc[4];

@@ -391,7 +391,11 @@ int dfu_reduce_partials_batch(const dfu_reduce_entry* entries, int32_t n, void* 
 
 /* ---------------------------------------------------------------- attention --------- */
 /* timm Attention with F.scaled_dot_product_attention: qkv bf16 [B*N][3][H][dh] (the qkv
- * Linear output), o bf16 [B*N][H][dh], lse fp32 [B*H][Npad]. dh == 64, N <= 256. */
+ * Linear output), o bf16 [B*N][H][dh], lse fp32 [B*H][Npad]. dh == 64, N <= 256.
+ * Domain (tests/test_attn_conformance_gpu.py): finite inputs.  The forwards write o and
+ * lse[:, 0..N) and leave lse[:, N..Npad) untouched; the backwards read lse[:, 0..N) only, accept
+ * any finite lse there (scores and lse of -110 included: no intermediate of a stored element
+ * overflows) and give the same bits whatever lse[:, N..Npad) holds.  delta is unused scratch. */
 int dfu_attention_fwd(const void* qkv, int32_t B, int32_t N, int32_t H, int32_t dh, float scale,
                       void* o, float* lse, void* stream);
 /* The "parity" precision mode's fp16 forward: qkv fp16 (the DFU_EPI_F16_DUAL output), the same
