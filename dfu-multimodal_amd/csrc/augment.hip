@@ -6,6 +6,11 @@
 //                                 22-bit fixed-point taps, horizontal pass then vertical, each
 //                                 rounded to u8 (k_resize_h, k_resize_v; taps from
 //                                 dfu_resize_coeffs on the host)
+//   standardize_images.py         the reference's offline letterbox (scripts/standardize_images.py:
+//                                 58-76) in place of the Resize: the same two passes with each
+//                                 image's own out_w x out_h, written at (pad_x, pad_y) of a black
+//                                 T x T canvas (k_letterbox_h, k_letterbox_v: the second pass
+//                                 writes box and border, every byte once; dfu_letterbox_batch)
 //   Random{Horizontal,Vertical}Flip, RandomRotation(30), ColorJitter(0.3, 0.3, 0.3),
 //   RandomAffine(20, (0.1, 0.1), (0.8, 1.2)), ToTensor, Normalize
 //                                 one gather kernel per output pixel (k_augment_apply): PIL's
@@ -97,6 +102,69 @@ __global__ void k_resize_v(const uint8_t* __restrict__ tmp, const dfu_resize_des
     out[i * 3] = (uint8_t)clip8(s0);
     out[i * 3 + 1] = (uint8_t)clip8(s1);
     out[i * 3 + 2] = (uint8_t)clip8(s2);
+  }
+}
+
+// Letterbox (dfu_letterbox_batch): the two passes above with per-image output sizes.  boxes:
+// int32 [n][4] = out_w, out_h, pad_x, pad_y.
+constexpr int kBoxW = 0, kBoxH = 1, kBoxX = 2, kBoxY = 3;
+
+// One output pixel of a pass: cnt taps k over the source pixels p, p + stride, ...
+DFU_DEV void tap_sum(const uint8_t* p, int64_t stride, const int32_t* k, int cnt, uint8_t* o) {
+  int s0 = 1 << (kPrec - 1), s1 = s0, s2 = s0;
+  for (int j = 0; j < cnt; ++j) {
+    const int w = k[j];
+    const uint8_t* q = p + j * stride;
+    s0 += q[0] * w;
+    s1 += q[1] * w;
+    s2 += q[2] * w;
+  }
+  o[0] = (uint8_t)clip8(s0);
+  o[1] = (uint8_t)clip8(s1);
+  o[2] = (uint8_t)clip8(s2);
+}
+
+// k_resize_h with the image's own output width: tmp[img][y][x], h x out_w.
+__global__ void k_letterbox_h(const uint8_t* __restrict__ src,
+                              const dfu_resize_desc* __restrict__ d,
+                              const int32_t* __restrict__ boxes,
+                              const int32_t* __restrict__ coefs, uint8_t* __restrict__ tmp) {
+  const dfu_resize_desc D = d[blockIdx.y];
+  const int OW = boxes[4 * blockIdx.y + kBoxW];
+  const int32_t* bnd = coefs + D.coef_off;
+  const int32_t* kk = bnd + 2 * OW;
+  const int64_t n = (int64_t)D.h * OW;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int y = (int)(i / OW), x = (int)(i % OW);
+    tap_sum(src + D.src_off + ((int64_t)y * D.w + bnd[2 * x]) * 3, 3, kk + (int64_t)x * D.ksh,
+            bnd[2 * x + 1], tmp + D.tmp_off + i * 3);
+  }
+}
+
+// Vertical pass onto the T x T canvas: one thread per canvas pixel, which is either a pixel of
+// the box (the vertical taps over tmp) or border (0); every byte of dst is written once.
+__global__ void k_letterbox_v(const uint8_t* __restrict__ tmp,
+                              const dfu_resize_desc* __restrict__ d,
+                              const int32_t* __restrict__ boxes,
+                              const int32_t* __restrict__ coefs, int T,
+                              uint8_t* __restrict__ dst) {
+  const dfu_resize_desc D = d[blockIdx.y];
+  const int32_t* box = boxes + 4 * blockIdx.y;
+  const int OW = box[kBoxW], OH = box[kBoxH], px = box[kBoxX], py = box[kBoxY];
+  const int32_t* bnd = coefs + D.coef_off + 2 * OW + (int64_t)OW * D.ksh;
+  const int32_t* kk = bnd + 2 * OH;
+  const int n = T * T;
+  uint8_t* out = dst + (int64_t)blockIdx.y * n * 3;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const int y = i / T - py, x = i % T - px;
+    uint8_t* o = out + (int64_t)i * 3;
+    if (x >= 0 && x < OW && y >= 0 && y < OH) {
+      tap_sum(tmp + D.tmp_off + ((int64_t)bnd[2 * y] * OW + x) * 3, (int64_t)OW * 3,
+              kk + (int64_t)y * D.ksv, bnd[2 * y + 1], o);
+    } else {
+      o[0] = o[1] = o[2] = 0;
+    }
   }
 }
 
@@ -402,6 +470,22 @@ extern "C" int dfu_resize_batch(const uint8_t* src, const dfu_resize_desc* descs
   const int gx = (out_w * out_h + TPB - 1) / TPB;
   hipLaunchKernelGGL(k_resize_v, dim3(gx < 64 ? gx : 64, n), dim3(TPB), 0, (hipStream_t)stream,
                      tmp, descs, coefs, out_w, out_h, dst);
+  DFU_LAUNCH_CHECK();
+  return DFU_OK;
+}
+
+extern "C" int dfu_letterbox_batch(const uint8_t* src, const dfu_resize_desc* descs,
+                                   const int32_t* boxes, const int32_t* coefs, int32_t n,
+                                   int32_t T, uint8_t* tmp, uint8_t* dst, void* stream) {
+  DFU_CHECK_ARG(src && descs && boxes && coefs && tmp && dst, "dfu_letterbox_batch: null pointer");
+  DFU_CHECK_ARG(n > 0 && n <= 65535 && T > 0 && (int64_t)T * T * 3 < (1ll << 31),
+                "dfu_letterbox_batch: n %d, T %d", n, T);
+  hipLaunchKernelGGL(k_letterbox_h, dim3(96, n), dim3(TPB), 0, (hipStream_t)stream, src, descs,
+                     boxes, coefs, tmp);
+  DFU_LAUNCH_CHECK();
+  const int gx = (T * T + TPB - 1) / TPB;
+  hipLaunchKernelGGL(k_letterbox_v, dim3(gx < 64 ? gx : 64, n), dim3(TPB), 0,
+                     (hipStream_t)stream, tmp, descs, boxes, coefs, T, dst);
   DFU_LAUNCH_CHECK();
   return DFU_OK;
 }

@@ -29,6 +29,17 @@ Test-time augmentation (notebooks/test_time_augmentation.py:145-167): `rgb_tta_t
 `thermal_tta_transform` put the rotation before the flips (TransformSpec.order) and use a bare
 RandomAffine without a scale; `views=K` on the preprocessor and the loaders gives K views per
 image from one decode, one copy and one resize (dfu_augment_views; tests/test_tta_gpu.py).
+
+Aspect-preserving standardisation (scripts/standardize_images.py:58-76, the step that makes the
+`*_standardized` trees notebooks/ablation_study.py reads): `standardized(spec)` sets
+TransformSpec.standardize = T, and the first device stage is then the script's letterbox in
+place of the Resize — each image resized to its own `letterbox_dims` (longest edge T, PIL
+bilinear) and placed centred on a black T x T canvas (dfu_letterbox_batch), pinned against PIL's
+own resize + paste (tests/test_standardize_gpu.py).  The random ops, `views=K` and the blur read
+the canvas unchanged; the batch still crosses PCIe as one copy.  This equals the reference's disk
+flow bit for bit only for losslessly stored trees (PNG, BMP, TIFF): the script re-encodes a .jpg
+at quality 95 and training decodes that.  data/standardize.py is the offline tool that writes
+those files.
 """
 import ctypes
 import math
@@ -75,10 +86,21 @@ class TransformSpec:
                                               # after the affine
     blur_p: float = 0.0                       # RandomApply's p; None = a bare GaussianBlur
     blur_kernel: int = 3                      # GaussianBlur kernel_size: only 3 is implemented
+    standardize: int = None                   # T: standardize_images.py's letterbox to T x T
+                                              # first, then the Compose; size must be (T, T)
 
     def __post_init__(self):
         if self.blur_kernel != 3:
             raise NotImplementedError(f"GaussianBlur kernel_size {self.blur_kernel}: only 3")
+        if self.standardize is not None:
+            T = self.standardize
+            if not isinstance(T, int) or T < 1:
+                raise ValueError(f"standardize = {T!r}: a positive target edge")
+            if tuple(self.size) != (T, T):
+                # the reference's Resize((224, 224)) on a standardised 224 x 224 file is PIL's
+                # copy; another size would be a second resample of the canvas
+                raise NotImplementedError(f"standardize {T} with Resize{tuple(self.size)}: "
+                                          f"only size == ({T}, {T})")
 
     @property
     def random(self):
@@ -109,6 +131,32 @@ thermal_tta_transform = TransformSpec(hflip_p=0.5, vflip_p=0.5, rotation=15,
                                       mean=THERMAL_MEAN, std=THERMAL_STD, order="rotate_flip")
 ORDERS = {"flip_rotate": L.DFU_AUG_ORDER_FLIP_ROTATE,
           "rotate_flip": L.DFU_AUG_ORDER_ROTATE_FLIP}  # enum dfu_aug_order
+
+
+def standardized(spec, target=224):
+    """`spec` on standardize_images.py's output: letterbox the raw image to target x target,
+    then the spec as before (what the reference computes from its *_standardized trees)."""
+    return replace(spec, standardize=target)
+
+
+def letterbox_dims(w, h, target):
+    """standardize_images.py:58-73 for a w x h image: (out_w, out_h, pad_x, pad_y), the
+    script's own float expressions.  The double rounding is the script's: int(m * (target / m))
+    is target - 1 for some longest edges m (55, 71, 83, ... at 224), and such an image keeps a
+    one-pixel black strip on the right or bottom.
+    ValueError where an output side is 0 (PIL's resize raises there and the script counts the
+    image as an error).  NotImplementedError where the short output side is below 3: for very
+    thin images PIL's resize gives the bytes of the vertical pass first, which the kernels
+    (horizontal first) do not model; every such case met has out_w <= 2."""
+    scale = target / max(w, h)
+    out_w = int(w * scale)
+    out_h = int(h * scale)
+    if out_w == 0 or out_h == 0:
+        raise ValueError(f"letterbox {w} x {h} -> {out_w} x {out_h}: height and width must be > 0")
+    if min(out_w, out_h) < 3:
+        raise NotImplementedError(f"letterbox {w} x {h} -> {out_w} x {out_h}: short side "
+                                  f"below 3 (PIL's pass order for thin images)")
+    return out_w, out_h, (target - out_w) // 2, (target - out_h) // 2
 
 
 @dataclass
@@ -317,16 +365,31 @@ class GpuPreprocessor:
             if im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
                 raise ValueError(f"expected H x W x 3 uint8 images, got {im.shape}")
         desc = np.zeros(n, RESIZE_DESC)
+        # spec.standardize: each image's letterbox box, int32 [n][4] (dfu_letterbox_batch)
+        T = spec.standardize
+        boxes = np.zeros((n if T is not None else 0, 4), np.int32)
         taps, coef_len, src_len, tmp_len = [], 0, 0, 0
         for i, im in enumerate(imgs):
             h, w = im.shape[:2]
-            kh, bh, wh = resize_taps(w, OW)
-            kv, bv, wv = resize_taps(h, OH)
+            ow, oh = OW, OH
+            if T is not None:
+                try:
+                    ow, oh, pad_x, pad_y = letterbox_dims(w, h, T)
+                except (ValueError, NotImplementedError) as e:
+                    raise type(e)(f"image {i} of the batch: {e}") from None
+                # the entry point cannot read device records: what it requires is checked here
+                if not (0 < ow <= T and 0 < oh <= T and 0 <= pad_x <= T - ow
+                        and 0 <= pad_y <= T - oh):
+                    raise ValueError(f"image {i} of the batch: box {ow} x {oh} at "
+                                     f"({pad_x}, {pad_y}) leaves the {T} x {T} canvas")
+                boxes[i] = (ow, oh, pad_x, pad_y)
+            kh, bh, wh = resize_taps(w, ow)
+            kv, bv, wv = resize_taps(h, oh)
             desc[i] = (src_len, tmp_len, coef_len, w, h, kh, kv)
             taps.append((bh, wh, bv, wv))
             coef_len += bh.size + wh.size + bv.size + wv.size
             src_len += im.size
-            tmp_len += h * OW * 3
+            tmp_len += h * ow * 3
         rec = pack_params(params, spec)
         # with views, each record's source image follows the records: view_src int32 [n * K]
         view_src = (np.repeat(np.arange(n, dtype=np.int32), views) if views is not None
@@ -334,9 +397,9 @@ class GpuPreprocessor:
         # with a blur, each record's 1-D weights: blur_k fp32 [nv][3], zeros = not blurred
         blur_k = (blur_weight_rows([p.blur for p in params]) if spec.blur is not None
                   else np.empty(0, np.float32))
-        # one staging buffer: [descs | params, view_src | blur_k | taps | pixels], 256-byte aligned
-        # sections (no blur_k section without spec.blur)
-        o_par = _align(desc.nbytes)
+        # one staging buffer: [descs, boxes | params, view_src | blur_k | taps | pixels], 256-byte
+        # aligned sections (no boxes without spec.standardize, no blur_k section without spec.blur)
+        o_par = _align(desc.nbytes + boxes.nbytes)
         o_blur = o_par + _align(rec.nbytes + view_src.nbytes)
         o_coef = o_blur + _align(blur_k.nbytes)
         o_src = o_coef + _align(coef_len * 4)
@@ -344,6 +407,7 @@ class GpuPreprocessor:
         stage = torch.empty(total, dtype=torch.uint8, pin_memory=self.device.type == "cuda")
         buf = stage.numpy()
         buf[:desc.nbytes] = desc.view(np.uint8)
+        buf[desc.nbytes:desc.nbytes + boxes.nbytes] = boxes.reshape(-1).view(np.uint8)
         buf[o_par:o_par + rec.nbytes] = rec.view(np.uint8)
         buf[o_par + rec.nbytes:o_par + rec.nbytes + view_src.nbytes] = view_src.view(np.uint8)
         buf[o_blur:o_blur + blur_k.nbytes] = blur_k.reshape(-1).view(np.uint8)
@@ -359,25 +423,51 @@ class GpuPreprocessor:
             at += im.size
         return _Staged(stage.to(self.device, non_blocking=True), n, o_par, o_coef, o_src,
                        tmp_len, views, o_par + rec.nbytes,
-                       o_blur if spec.blur is not None else None)
+                       o_blur if spec.blur is not None else None,
+                       desc.nbytes if T is not None else None)
+
+    def resize(self, st, out=None):
+        """First device stage of a staged batch: uint8 [n, H, W, 3], the resized images, or with
+        spec.standardize the letterboxed canvases (what standardize_images.py saves).  `out`: a
+        contiguous uint8 CUDA tensor of that many bytes to write into; every byte is written."""
+        OH, OW = self.spec.size
+        if out is None:
+            out = torch.empty((st.n, OH, OW, 3), dtype=torch.uint8, device=self.device)
+        if (out.dtype != torch.uint8 or out.numel() != st.n * OH * OW * 3
+                or not out.is_contiguous() or out.device.type != "cuda"):
+            raise ValueError("out: a contiguous uint8 CUDA tensor of n * H * W * 3 bytes")
+        if st.n == 0:
+            return out
+        lib = L.load()
+        base = st.dev.data_ptr()
+        tmp = torch.empty(st.tmp_len, dtype=torch.uint8, device=self.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if st.o_box is not None:  # spec.standardize: the letterbox in place of the resize
+            check(lib.dfu_letterbox_batch(ctypes.c_void_p(base + st.o_src), ctypes.c_void_p(base),
+                                          ctypes.c_void_p(base + st.o_box),
+                                          ctypes.c_void_p(base + st.o_coef), st.n, OH,
+                                          ctypes.c_void_p(tmp.data_ptr()),
+                                          ctypes.c_void_p(out.data_ptr()), stream),
+                  "dfu_letterbox_batch")
+        else:
+            check(lib.dfu_resize_batch(ctypes.c_void_p(base + st.o_src), ctypes.c_void_p(base),
+                                       ctypes.c_void_p(base + st.o_coef), st.n, OW, OH,
+                                       ctypes.c_void_p(tmp.data_ptr()),
+                                       ctypes.c_void_p(out.data_ptr()), stream),
+                  "dfu_resize_batch")
+        return out
 
     def run(self, st):
-        """Device side: resize + augment + normalise a staged batch (4 launches); a batch staged
-        with views gives [n * K, 3, H, W], sample-major (dfu_augment_views).  A spec with a blur
-        goes through dfu_augment_blur instead, with or without views."""
+        """Device side: resize (or letterbox) + augment + normalise a staged batch (4 launches);
+        a batch staged with views gives [n * K, 3, H, W], sample-major (dfu_augment_views).  A
+        spec with a blur goes through dfu_augment_blur instead, with or without views."""
         OH, OW = self.spec.size
         if st.n == 0:
             return torch.empty((0, 3, OH, OW), dtype=torch.float32, device=self.device)
         lib = L.load()
         base = st.dev.data_ptr()
-        tmp = torch.empty(st.tmp_len, dtype=torch.uint8, device=self.device)
-        resized = torch.empty(st.n * OH * OW * 3, dtype=torch.uint8, device=self.device)
+        resized = self.resize(st)
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        check(lib.dfu_resize_batch(ctypes.c_void_p(base + st.o_src), ctypes.c_void_p(base),
-                                   ctypes.c_void_p(base + st.o_coef), st.n, OW, OH,
-                                   ctypes.c_void_p(tmp.data_ptr()),
-                                   ctypes.c_void_p(resized.data_ptr()), stream),
-              "dfu_resize_batch")
         if self.spec.blur is not None:
             nv = st.n * (st.views or 1)
             out = torch.empty((nv, 3, OH, OW), dtype=torch.float32, device=self.device)
@@ -424,6 +514,7 @@ class _Staged:
     views: int = None      # K parameter records per image (dfu_augment_views), None: one each
     o_view: int = 0        # view_src int32 [n * K]
     o_blur: int = None     # blur_k fp32 [n * K][3] (dfu_augment_blur), None: a spec without blur
+    o_box: int = None      # boxes int32 [n][4] (dfu_letterbox_batch), None: a plain Resize
 
 
 def decode_rgb(path):

@@ -643,6 +643,20 @@ int dfu_resize_coeffs(int32_t in_size, int32_t out_size, int32_t* bounds, int32_
 int dfu_resize_batch(const uint8_t* src, const dfu_resize_desc* descs, const int32_t* coefs,
                      int32_t n, int32_t out_w, int32_t out_h, uint8_t* tmp, uint8_t* dst,
                      void* stream);
+/* Aspect-preserving standardisation (scripts/standardize_images.py:58-76) of n packed images
+ * onto black T x T canvases: image i is resized to its own out_w x out_h (PIL
+ * Image.resize(BILINEAR): the two passes of dfu_resize_batch, each rounded to u8) and placed
+ * with its top-left corner at (pad_x, pad_y); every canvas byte outside that box is 0.
+ * dst n*T*T*3 is dfu_resize_batch's layout, so the dfu_augment_* calls consume it unchanged; the
+ * second pass writes every byte of dst exactly once, box or border (dst needs no clearing).
+ * descs: dfu_resize_desc with tmp_off / coef_off / ksh / ksv for the image's own out_w, out_h
+ * (tmp holds sum_i h_i*out_w_i*3 bytes).  boxes: device int32 [n][4] = out_w, out_h, pad_x,
+ * pad_y per image, with 0 < out <= T and 0 <= pad, pad + out <= T each way: the caller checks
+ * that before the call (device arrays cannot be read here).  src readable up to 3 bytes past
+ * the last image, as dfu_resize_batch.  n <= 65535. */
+int dfu_letterbox_batch(const uint8_t* src, const dfu_resize_desc* descs, const int32_t* boxes,
+                        const int32_t* coefs, int32_t n, int32_t T, uint8_t* tmp, uint8_t* dst,
+                        void* stream);
 /* Flips, rotation, colour jitter, affine, ToTensor and Normalize on n resized H x W x 3 u8
  * images -> out fp32 [n][3][H][W].  params and contrast_means (n int32 scratch) are device
  * arrays (contrast_means receives the per-image grey sums); mean3 / std3 are host

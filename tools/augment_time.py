@@ -1,8 +1,10 @@
 """Time the GPU input pipeline on a batch of decoded images: the whole GpuPreprocessor call (host
 staging + one H2D copy + the two HIP kernels) on a host clock, and the reference's per-sample
 PIL/torch transform on one host core for comparison.  --spec picks the train transform: rgb (the
-default), thermal, or thermal_only (the thermal one plus the GaussianBlur of
-train_thermal_only.py; the host reference has no blur, so its figure is of the other ops)."""
+default), thermal, thermal_only (the thermal one plus the GaussianBlur of
+train_thermal_only.py; the host reference has no blur, so its figure is of the other ops), or
+standardized (the rgb one after standardize_images.py's letterbox: dfu_letterbox_batch in place
+of dfu_resize_batch; the host reference letterboxes with PIL first)."""
 import argparse
 import os
 import sys
@@ -15,7 +17,17 @@ import torch
 from data import gpu_transforms as GT
 
 SPECS = {"rgb": GT.rgb_train_transform, "thermal": GT.thermal_train_transform,
-         "thermal_only": GT.thermal_only_train_transform}
+         "thermal_only": GT.thermal_only_train_transform,
+         "standardized": GT.standardized(GT.rgb_train_transform)}
+
+
+def _letterbox(im, target):
+    """standardize_images.py's resize + paste on the host."""
+    from PIL import Image
+    ow, oh, px, py = GT.letterbox_dims(im.shape[1], im.shape[0], target)
+    canvas = Image.new("RGB", (target, target), color=0)
+    canvas.paste(Image.fromarray(im).resize((ow, oh), Image.BILINEAR), (px, py))
+    return np.asarray(canvas)
 
 
 def main():
@@ -49,6 +61,8 @@ def main():
     t0 = time.perf_counter()
     n = min(8, a.batch)
     for im, p in zip(imgs[:n], params[:n]):
+        if spec.standardize is not None:
+            im = _letterbox(im, spec.standardize)
         TR.reference_transform(im, spec.size, spec.mean, spec.std, p.hflip, p.vflip, p.angle,
                                p.ops, p.affine)
     cpu = (time.perf_counter() - t0) / n
